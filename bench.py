@@ -4,6 +4,12 @@ python bench.py --gpus N --steps K --warmup W   (N > 1 under torch.distributed.r
 python bench.py --config c3 [--gpus N]          (BASELINE.json configs[2]: 4-OAK bracket rig, 8 streams)
 python bench.py --config c4                     (BASELINE.json configs[3]: 1280x800, K=4000, + local BA)
 python bench.py --config c5 [--gpus 4]          (BASELINE.json configs[4]: 4-camera RGB-D rig 1280x720, one camera per GPU)
+python bench.py ... --full                      (every leg below marked [--full], after the timed steps)
+python bench.py ... --dump-outputs DIR          (the last timed step's poses as DIR/<name>.npy)
+
+* a plain run sets up, warms up, times the K steps and prints the result line (value,
+  ms_per_step, the dominant kernel's live roofline); the legs marked [--full] take runs of their
+  own after the timed steps and are reported only with ``--full``.
 
 * N = 1, config c2 (BASELINE.json configs[1]): one stereo pair 640x400, K=2000 ORB-style
   keypoints per image, synthetic room sequence; a *step* = one batch of ``--batch`` synchronised
@@ -22,13 +28,15 @@ python bench.py --config c5 [--gpus 4]          (BASELINE.json configs[4]: 4-cam
   replay of ``--unique`` rendered frames, so consecutive frames stay consecutive in time).
 * timing: barrier + synchronize on both sides of exactly K steps; MAX over ranks.
 * roofline: per-kernel HIP-event timing of the timed steps on the stream each kernel runs on,
-  for the dominant kernel: algorithmic bytes / average duration vs 8 TB/s.
-* cpu_baseline (rank 0, N = 1): the NumPy oracle on a bounded sample of the same frames, over
+  for the dominant kernel: algorithmic bytes / average duration vs 8 TB/s; [--full] the same
+  kernels alone on one stream (per_kernel_us_isolated, roofline.isolated), the pose stage on
+  outlier-laden data (pose_with_outliers) and the B = 1 latency (latency_b1_ms).
+* cpu_baseline [--full] (rank 0, N = 1): the NumPy oracle on a bounded sample of the same frames, over
   the host cores this process may use, plus the one-process figure.
-* boundary (c2, N = 1): HipSlamEngine.process_frames on host SynchronizedFrameSets from the
+* boundary [--full] (c2, N = 1): HipSlamEngine.process_frames on host SynchronizedFrameSets from the
   CameraRig (the drop-in boundary, scripts/run_slam.py:314-328) at batch 1 and 64.
 * --config c4: the same step plus the A8 stage (every 5th frame a keyframe of a 10-keyframe
-  window, 5 Gauss-Newton iterations per keyframe); the roofline is then that of the dominant
+  window, 5 Gauss-Newton iterations per keyframe); [--full] the roofline is then that of the dominant
   kernel of the step, the FP64-MFMA Schur product when it dominates (HIP events around its launches).
 * --config c5: the 4-camera RGB-D rig (BGR u8 + aligned u16 mm depth, 1280x720 per camera, the
   cameras on the brackets.urdf joints): per camera the colour image is converted on the device,
@@ -187,6 +195,27 @@ def triangle_indices(total: int, unique: int) -> np.ndarray:
     period = 2 * (unique - 1)
     k = np.arange(total) % period
     return np.where(k < unique, k, period - k)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath: str, arrays: dict) -> None:
+    """--dump-outputs: every array as DIR/<name>.npy, float32 stays float32 and everything else
+    (f64 poses and covariances, i32 status records: exact in f64) becomes float64.  When they
+    exceed 64 MB together, every array over its equal share of the limit is cut to a fixed, seeded
+    sample of its flattened elements."""
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float32 if np.asarray(a).dtype == np.float32 else np.float64)
+              for name, a in arrays.items()}
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    over = sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES
+    for name, a in arrays.items():
+        if over and a.nbytes > share:
+            pick = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[pick]
+        np.save(d / f"{name}.npy", a)
 
 
 # ---- algorithmic bytes (SURVEY.md §8d) --------------------------------------------------------
@@ -870,13 +899,21 @@ def run_single(args, world: int, rank: int, dev_index: int) -> dict:
         elapsed = float(tt.item())
     res = h.read_poses(B)
     ok_frac = float(np.mean(res["stats"][:, :, 0] == 0))
-    rig_ok = float(np.mean(h.read_rig_poses(B)["stats"][:, 0] == 0)) if P > 1 else None
+    res_rig = h.read_rig_poses(B) if P > 1 else None
+    rig_ok = float(np.mean(res_rig["stats"][:, 0] == 0)) if P > 1 else None
+    if args.dump_outputs and rank == 0:
+        dump = {f"pose_{k}": v for k, v in res.items()}
+        if res_rig is not None:
+            dump.update({f"rig_{k}": v for k, v in res_rig.items()})
+        if "tsdf" in names:
+            dump["tsdf"], dump["tsdf_weight"] = h.tsdf_read()
+        dump_outputs(args.dump_outputs, dump)
 
     # ---- the same kernels run alone (after the timed region, one stream, 3 batches): under the
     # two-stream pipeline a kernel shares the GPU with the other stream's kernels, so its timed
     # duration above includes that sharing; these isolated durations are the kernel's own speed
-    iso_us = {k: 0.0 for k in kern}
-    n_iso = 3
+    iso_us = {k: 0.0 for k in kern} if args.full else None
+    n_iso = 3 if args.full else 0
     torch.cuda.synchronize()
     for r in range(n_iso):
         s_iso = r % (args.warmup + args.steps)   # replayed input: only the durations are used
@@ -897,7 +934,7 @@ def run_single(args, world: int, rank: int, dev_index: int) -> dict:
     # --outliers % of every frame's refined temporal positions made outliers before the pose
     # kernels, so the bounded RANSAC scoring cannot end at the first correct root
     pose_outliers = None
-    if args.outliers > 0 and args.outlier_steps > 0 and not (c4 or c5):
+    if args.full and args.outliers > 0 and args.outlier_steps > 0 and not (c4 or c5):
         ev_o = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in names]
                 for _ in range(args.outlier_steps)]
         base_s = args.warmup + args.steps
@@ -953,7 +990,7 @@ def run_single(args, world: int, rank: int, dev_index: int) -> dict:
     dom_bytes = unit_bytes * B          # §8d per-frame bytes x the frames one launch processes
     # C4's MFMA kernel: back-to-back replays of k_ba_schur on the last solved window, between two
     # HIP events (per-launch events inside the timed steps would add their own gaps to the BA chain)
-    schur = h.ba_replay_schur(0, 50, sp) if c4 else None
+    schur = h.ba_replay_schur(0, 50, sp) if c4 and args.full else None
     front = {k: v for k, v in per_kernel_us.items() if k not in ("local_ba", "tsdf")}
     if not front:
         raise SystemExit("--kernel-events must name at least one front-end kernel (the roofline's live launch time)")
@@ -975,7 +1012,7 @@ def run_single(args, world: int, rank: int, dev_index: int) -> dict:
 
     # ---- B = 1 latency: one frame submitted and its pose read back -------------
     lat_ms = None
-    if rank == 0 and args.latency_frames > 0:
+    if args.full and rank == 0 and args.latency_frames > 0:
         h1 = Handle(rects, cfg, max_batch=1, device=dev_index)
         if P > 1:
             h1.set_rig(E)
@@ -1004,18 +1041,19 @@ def run_single(args, world: int, rank: int, dev_index: int) -> dict:
         "algorithmic_bytes_per_frame": unit_bytes,
         "frames_per_launch": B,
         "avg_launch_us": per_kernel_us[dom],
-        "largest_isolated_kernel": max(iso_us, key=iso_us.get),
+        "largest_isolated_kernel": max(iso_us, key=iso_us.get) if args.full else None,
         "kernel_own_bytes_per_launch": None if c5 else kernel_bytes(dom, B, h, cfg, rect.is_identity, n_img),
         "end_to_end_hbm_frac": unit_bytes * (frames_total / elapsed / world) / (HBM_PEAK_GBS * 1e9),
         "valu": valu,
     }
     # the dominant kernel measured alone: the same algorithmic bytes (and PMC VALU instructions)
     # over its isolated duration
-    iso = {"avg_launch_us": iso_us[dom], "achieved": dom_bytes / (iso_us[dom] * 1e-6) / 1e9}
-    iso["frac"] = iso["achieved"] / HBM_PEAK_GBS
-    if valu is not None:
-        iso["valu_frac"] = valu["insts_per_launch"] / (iso_us[dom] * 1e-6) / VALU_PEAK_WINST
-    roofline["isolated"] = iso
+    if args.full:
+        iso = {"avg_launch_us": iso_us[dom], "achieved": dom_bytes / (iso_us[dom] * 1e-6) / 1e9}
+        iso["frac"] = iso["achieved"] / HBM_PEAK_GBS
+        if valu is not None:
+            iso["valu_frac"] = valu["insts_per_launch"] / (iso_us[dom] * 1e-6) / VALU_PEAK_WINST
+        roofline["isolated"] = iso
     if mfma is not None and mfma["time_per_step_us"] > per_kernel_us[dom]:
         roofline, front_roofline = mfma, roofline   # the Schur product is the step's dominant kernel
     else:
@@ -1081,9 +1119,12 @@ def run_single(args, world: int, rank: int, dev_index: int) -> dict:
         out["front_end_roofline"] = front_roofline
     if "tsdf" in names:
         out["dense_map"] = tsdf_report(h, per_kernel_us["tsdf"], B, width, height)
-        out["dense_map"]["outputs"] = dense_outputs_report(h)
+        if args.full:
+            out["dense_map"]["outputs"] = dense_outputs_report(h)
     h.close()
     destroy_masked_streams()
+    if not args.full:
+        return out
     if rank == 0 and world == 1 and args.boundary_frames > 0 and args.config == "c2":
         out["boundary"] = boundary_bench(uniq, src, args.boundary_frames)
         if args.default_frames > 0:
@@ -1241,6 +1282,11 @@ def run_sharded(args, world: int, rank: int, dev_index: int) -> dict:
         per_kernel_us = timer.mean_us()
         sb, pr = rig.rk.block, rig.rk.record
         pb = rig.rk.pblock if c5 else 0
+    if args.dump_outputs and rank == 0:
+        dump = {f"pose_{k}": v for k, v in res["pairs"].items()}
+        if P > 1:
+            dump.update({f"rig_{k}": v for k, v in res["rig"].items()})
+        dump_outputs(args.dump_outputs, dump)
     ok = float(np.mean(res["pairs"]["stats"][:, :, 0] == 0))
     rig_ok = float(np.mean(res["rig"]["stats"][:, 0] == 0)) if P > 1 else None
     # exchange spans (HIP events across the streams): not kernels, reported on their own
@@ -1407,6 +1453,13 @@ def main() -> None:
                     help="BASELINE.json configs[1] (c2), configs[2] (c3), configs[3] (c4) or configs[4] (c5)")
     ap.add_argument("--batch", type=int, default=0, help="frames per step (0 = C2_BATCH for c2, 256 for c3, 50 for c4, 128 for c5)")
     ap.add_argument("--unique", type=int, default=0, help="distinct rendered frames, triangle-wave replay (0 = C2_UNIQUE for c2, 48 for c3, 24 for c4 / c5)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (isolated per-kernel times, the pose stage "
+                         "with outliers, B=1 latency, the C4 Schur replay, dense-map outputs, the host boundary, the "
+                         "default drop-in path, the CPU baseline); the options below that size those legs apply with it")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write what the last timed step computed (the arrays read_poses / read_rig_poses return, "
+                         "with --tsdf the volume) as DIR/<name>.npy, float32 or float64")
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of oracle CPU baseline (0 = skip)")
     ap.add_argument("--cpu-procs", type=int, default=0, help="oracle processes for the CPU baseline (0 = usable CPUs)")
     ap.add_argument("--latency-frames", type=int, default=20, help="B=1 submissions timed for latency_b1_ms")

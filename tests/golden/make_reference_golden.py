@@ -102,12 +102,39 @@ def slampose(mods):
             "slam_config": {k: getattr(mods["interface"].SlamConfig(), k) for k in mods["interface"].SlamConfig.__dataclass_fields__}}
 
 
+def random_pose_matrices(n: int = 20, seed: int = 11) -> list:
+    """The seeded rigid transforms of tests/test_boundary.py::test_live_reference_slampose_random."""
+    from scipy.spatial.transform import Rotation
+
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(n):
+        m = np.eye(4)
+        m[:3, :3] = Rotation.from_rotvec(rng.normal(0, 2.0, 3)).as_matrix()
+        m[:3, 3] = rng.normal(size=3)
+        out.append(m)
+    return out
+
+
+def slampose_random(mods):
+    out = []
+    for m in random_pose_matrices():
+        p = mods["interface"].SlamPose.from_4x4_matrix(m, 1.0)
+        out.append({"rotation": p.rotation.tolist(), "back": p.to_4x4_matrix().tolist()})
+    return out
+
+
+LONG_TRACE_CALLS = 40   # the same scripted sources, three times as many calls as rig_sync
+
+
 def main():
     mods = load_reference()
     data = {
         "rig_sync": sync_trace(mods["rig"].CameraRig),
+        "rig_sync_long": sync_trace(mods["rig"].CameraRig, LONG_TRACE_CALLS),
         "world_extrinsics": world_extrinsics(mods),
         "slampose": slampose(mods),
+        "slampose_random": slampose_random(mods),
         "source": "reference thor_slam/camera/rig.py, types.py, slam/interface.py @ 2026-01-30",
     }
     (HERE / "reference_boundary.json").write_text(json.dumps(data, indent=1))

@@ -1,14 +1,13 @@
 """The restated boundary (types, CameraRig, RigCalibration, SlamPose, SlamEngine contract) against
-golden vectors captured from the reference's own code (tests/golden/make_reference_golden.py),
-plus live comparisons when /root/reference is present (build container only)."""
+golden vectors captured from the reference's own code (tests/golden/make_reference_golden.py)."""
 
 import json
 import math
+import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
-from scipy.spatial.transform import Rotation
 
 from helpers import scripted_sources
 from thor_slam_amd.camera import CAMERA_MAP, CameraRig, Extrinsics, FrameSet, RigCalibration, load_rig_extrinsics_from_urdf
@@ -16,17 +15,15 @@ from thor_slam_amd.camera.urdf import parse_urdf_transform
 from thor_slam_amd.slam import SlamConfig, SlamEngine, SlamMap, SlamPose, TrackingState
 
 GOLD = json.loads((Path(__file__).parent / "golden" / "reference_boundary.json").read_text())
-REF = Path("/root/reference")
 URDF = Path(__file__).parent / "golden" / "brackets_joints.json"
+BRACKETS_URDF = Path(__file__).parent / "golden" / "brackets.urdf"   # the reference's examples/assets/brackets.urdf
+sys.path.insert(0, str(Path(__file__).parent / "golden"))
 
 
-def _trace(rig_cls):
-    import sys
-
-    sys.path.insert(0, str(Path(__file__).parent / "golden"))
+def _trace(rig_cls, n_calls: int = 14):
     from make_reference_golden import sync_trace
 
-    return sync_trace(rig_cls)
+    return sync_trace(rig_cls, n_calls)
 
 
 def test_rig_sync_matches_reference_trace():
@@ -79,10 +76,7 @@ def test_urdf_loader_uses_intrinsic_xyz():
 
 
 def test_urdf_fixture_loads_four_cameras():
-    urdf = REF / "examples/assets/brackets.urdf"
-    if not urdf.exists():
-        pytest.skip("reference URDF not present (GPU box)")
-    ext = load_rig_extrinsics_from_urdf(urdf, CAMERA_MAP)
+    ext = load_rig_extrinsics_from_urdf(BRACKETS_URDF, CAMERA_MAP)
     assert sorted(ext) == sorted(CAMERA_MAP)
     fixture = json.loads(URDF.read_text())
     for k, e in ext.items():
@@ -130,34 +124,24 @@ def test_rig_rejects_bad_imu_source():
 
 
 # ------------------------------------------------------------------------------------------------
-# live comparisons against the reference code (build container only)
+# the former live comparisons against the reference code, on its recorded outputs
+# (tests/golden/make_reference_golden.py: rig_sync_long, slampose_random)
 # ------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def ref_mods():
-    if not (REF / "thor_slam").exists():
-        pytest.skip("/root/reference not present")
-    import sys
+def test_live_reference_rig_sync():
+    from make_reference_golden import LONG_TRACE_CALLS
 
-    sys.path.insert(0, str(Path(__file__).parent / "golden"))
-    from make_reference_golden import load_reference
-
-    return load_reference()
+    assert _trace(CameraRig, LONG_TRACE_CALLS) == GOLD["rig_sync_long"]
 
 
-def test_live_reference_rig_sync(ref_mods):
-    assert _trace(ref_mods["rig"].CameraRig) == _trace(CameraRig)
+def test_live_reference_slampose_random():
+    from make_reference_golden import random_pose_matrices
 
-
-def test_live_reference_slampose_random(ref_mods):
-    rng = np.random.default_rng(11)
-    for _ in range(20):
-        m = np.eye(4)
-        m[:3, :3] = Rotation.from_rotvec(rng.normal(0, 2.0, 3)).as_matrix()
-        m[:3, 3] = rng.normal(size=3)
-        a = ref_mods["interface"].SlamPose.from_4x4_matrix(m, 1.0)
+    mats = random_pose_matrices()
+    assert len(mats) == len(GOLD["slampose_random"]) == 20
+    for m, rec in zip(mats, GOLD["slampose_random"]):
         b = SlamPose.from_4x4_matrix(m, 1.0)
-        np.testing.assert_array_equal(a.rotation, b.rotation)
-        np.testing.assert_array_equal(a.to_4x4_matrix(), b.to_4x4_matrix())
+        np.testing.assert_array_equal(np.array(rec["rotation"]), b.rotation)
+        np.testing.assert_array_equal(np.array(rec["back"]), b.to_4x4_matrix())
 
 
 def test_fast_quaternion_equals_scipy():

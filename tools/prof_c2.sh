@@ -11,7 +11,7 @@ out=gpurun_out/$tag
 mkdir -p "$out"
 # the profiled runs skip the B = 1 / B = 64 boundary leg (its small launches would dominate the
 # per-kernel averages); the final bench line keeps it
-args=(--steps 20 --warmup 3 --cpu-budget 0 --latency-frames 0 --boundary-frames 0 --default-frames 0 "$@")
+args=(--full --steps 20 --warmup 3 --cpu-budget 0 --latency-frames 0 --boundary-frames 0 --default-frames 0 "$@")
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o run -- python3 bench.py "${args[@]}" > "$out/stats.log" 2>&1
 for c in FETCH_SIZE WRITE_SIZE "SQ_INSTS_VALU SQ_WAVES"; do
   n=${c%% *}
