@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define TSLAM_ABI_VERSION 20
+#define TSLAM_ABI_VERSION 21
 
 #define TSLAM_OK 0
 #define TSLAM_EINVAL (-1)
@@ -762,6 +762,40 @@ int tslam_mesh_read_colors(tslam_handle* h, float* colors, int64_t max_tris);
 int tslam_esdf_compute(tslam_handle* h, double max_dist, double site_vox, double min_weight, void* stream);
 int tslam_esdf_read(tslam_handle* h, float* esdf);
 int tslam_esdf_slice(tslam_handle* h, int y0, int y1, double max_dist, double site_vox, double min_weight, float* out);
+
+/* Dense stereo depth (ABI 21): a depth image from a rectified stereo pair, so that a stereo rig
+ * feeds the TSDF volume as an RGB-D camera does (the reference's stereo cameras compute depth
+ * themselves and hand nvblox a depth image).  Spec: thor_slam_amd/stereo_depth.py (census 7x7,
+ * Hamming cost, 5x5 box aggregation, winner-take-all, uniqueness, left-right check, sub-pixel in
+ * 1/32 px, depth = floor(fxb * 32000 / disp32 + 1/2) mm).  Stereo handles only.
+ *
+ * tslam_stereo_depth_init: parameters (n_disp 4..256, 0 = the handle's max_disparity clamped to
+ *   that range; uniqueness 0..99; lr_tol >= 0; reserved 0) and output slots for max_frames frames:
+ *   depth and disp32, u16 [max_frames][H][W], plus scratch.  May be called again (outside a
+ *   batch).  tslam_reset keeps parameters and buffers; tslam_destroy frees them.
+ * tslam_stereo_depth: pair `pair`'s frames first_frame .. first_frame + n_frames - 1 of the last
+ *   batch (their rectified level-0 images are ring-resident) into slots 0 .. n_frames - 1, with the
+ *   pair's fx * baseline.  Enqueued on `stream` (NULL: the handle's last stream); outside a batch.
+ * tslam_stereo_depth_images: the same matcher on caller-supplied rectified device images of
+ *   width x height (16 .. the handle's size each; dense rows; frames frame_stride bytes apart in
+ *   both `left` and `right`); the outputs are then dense [n_frames][height][width].
+ * tslam_stereo_depth_buffers: the device pointers and the bytes of one full-size slot.
+ * tslam_stereo_depth_read: slot `slot` of the last call copied out (synchronises), in that call's
+ *   image size; either pointer may be NULL.
+ * tslam_tsdf_integrate_rect: tslam_tsdf_integrate for depth images that already live in pair
+ *   `pair`'s RECTIFIED left camera (what tslam_stereo_depth writes): the voxel's pixel is looked up
+ *   directly, not through the raw camera's undistortion table. */
+typedef struct {
+    int32_t n_disp, uniqueness, lr_tol, reserved;
+} tslam_stereo_depth_params;
+int tslam_stereo_depth_init(tslam_handle* h, const tslam_stereo_depth_params* params, int max_frames);
+int tslam_stereo_depth(tslam_handle* h, int pair, int64_t first_frame, int n_frames, void* stream);
+int tslam_stereo_depth_images(tslam_handle* h, const uint8_t* left, const uint8_t* right, int64_t frame_stride,
+                              int width, int height, double fxb, int n_frames, void* stream);
+int tslam_stereo_depth_buffers(tslam_handle* h, void** depth, void** disp32, int64_t* frame_bytes);
+int tslam_stereo_depth_read(tslam_handle* h, int slot, uint16_t* depth, uint16_t* disp32);
+int tslam_tsdf_integrate_rect(tslam_handle* h, int pair, const void* depth, int64_t stride_bytes, int n_frames,
+                              int64_t first_frame, const double* world_T_cam, void* stream);
 
 #ifdef __cplusplus
 }

@@ -147,6 +147,14 @@ struct tslam_handle {
     TsdfArgs tsdf{};
     double* d_tsdf_poses = nullptr;   // [TSDF_MAX_FRAMES][TSDF_POSE]
     double* d_tsdf_wTc = nullptr;     // [TSDF_MAX_FRAMES][16] host poses staged
+    // dense stereo depth (tslam_stereo_depth_*): parameters, output slots and winner-map scratch
+    bool sd_on = false;
+    tslam_stereo_depth_params sd_prm{};
+    int sd_frames = 0;                // slots
+    int sd_w = 0, sd_h = 0;           // image size of the last call (layout of the slots)
+    uint16_t* d_sd_depth = nullptr;   // [sd_frames][H][W]
+    uint16_t* d_sd_disp = nullptr;
+    uint8_t* d_sd_win = nullptr;      // [2][sd_frames][H][W] left / right winners
     // dense-map outputs (tslam_mesh_* / tslam_esdf_*): scratch sized on first use
     uint8_t* d_mesh_cfg = nullptr;    // [cubes] configuration bytes
     uint32_t* d_mesh_bsum = nullptr;  // [blocks] triangle totals
@@ -2542,7 +2550,7 @@ int tslam_tsdf_init(tslam_handle* h, const double* origin, const int32_t* dims, 
 }
 
 static int tsdf_integrate(tslam_handle* h, int pair, const void* color, const void* depth, int64_t stride_bytes,
-                          int n_frames, int64_t first_frame, const double* world_T_cam, void* stream);
+                          int n_frames, int64_t first_frame, const double* world_T_cam, void* stream, bool rect = false);
 
 int tslam_tsdf_integrate(tslam_handle* h, int pair, const void* depth, int64_t stride_bytes, int n_frames,
                          int64_t first_frame, const double* world_T_cam, void* stream) {
@@ -2563,8 +2571,13 @@ int tslam_tsdf_color(tslam_handle* h, int enable) {
     return TSLAM_OK;
 }
 
+int tslam_tsdf_integrate_rect(tslam_handle* h, int pair, const void* depth, int64_t stride_bytes, int n_frames,
+                              int64_t first_frame, const double* world_T_cam, void* stream) {
+    return tsdf_integrate(h, pair, nullptr, depth, stride_bytes, n_frames, first_frame, world_T_cam, stream, true);
+}
+
 static int tsdf_integrate(tslam_handle* h, int pair, const void* color, const void* depth, int64_t stride_bytes,
-                          int n_frames, int64_t first_frame, const double* world_T_cam, void* stream) {
+                          int n_frames, int64_t first_frame, const double* world_T_cam, void* stream, bool rect) {
     if (!h || pair < 0 || pair >= h->P) return fail(TSLAM_EINVAL, "bad handle or pair");
     BA_FLUSH(h);
     if (!h->tsdf_on) return fail(TSLAM_ESTATE, "no TSDF volume (tslam_tsdf_init)");
@@ -2587,7 +2600,8 @@ static int tsdf_integrate(tslam_handle* h, int pair, const void* color, const vo
     a.fy = h->calib[pair].fy;
     a.cx = h->calib[pair].cx;
     a.cy = h->calib[pair].cy;
-    a.map = ((h->map_mask >> cam) & 1u) ? h->d_maps + (size_t)cam * h->W * h->H * 2 : nullptr;
+    // rect: the depth lives in the pair's rectified camera already (tslam_stereo_depth)
+    a.map = (!rect && ((h->map_mask >> cam) & 1u)) ? h->d_maps + (size_t)cam * h->W * h->H * 2 : nullptr;
     a.stride = stride_bytes;
     if (!color) a.col = a.col_w = nullptr;   // the colour layer keeps its state without colour input
     for (int b0 = 0; b0 < n_frames; b0 += TSDF_MAX_FRAMES) {
@@ -2604,6 +2618,118 @@ static int tsdf_integrate(tslam_handle* h, int pair, const void* color, const vo
         HIPCHK(hipGetLastError());
         if (world_T_cam) HIPCHK(hipStreamSynchronize(s));   // the staged host poses are reused
     }
+    return TSLAM_OK;
+}
+
+// -- dense stereo depth ------------------------------------------------------------------------------
+int tslam_stereo_depth_init(tslam_handle* h, const tslam_stereo_depth_params* params, int max_frames) {
+    if (!h || !params) return fail(TSLAM_EINVAL, "bad argument");
+    if (h->prm.rgbd) return fail(TSLAM_ESTATE, "dense stereo depth needs a stereo handle (this one is RGB-D)");
+    if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_stereo_depth_init inside a batch");
+    tslam_stereo_depth_params p = *params;
+    if (p.n_disp == 0) p.n_disp = std::min(256, std::max(4, (int)h->prm.max_disparity));
+    if (p.n_disp < 4 || p.n_disp > 256) return fail(TSLAM_EINVAL, "n_disp must be 4..256 (0 = max_disparity)");
+    if (p.uniqueness < 0 || p.uniqueness > 99) return fail(TSLAM_EINVAL, "uniqueness must be 0..99");
+    if (p.lr_tol < 0 || p.reserved != 0) return fail(TSLAM_EINVAL, "lr_tol must be >= 0 and reserved 0");
+    if (max_frames < 1 || max_frames > 65535) return fail(TSLAM_EINVAL, "max_frames must be 1..65535");
+    BA_FLUSH(h);
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceSynchronize());
+    const size_t px = (size_t)max_frames * h->W * h->H;
+    int rc = dev_realloc(h, (void**)&h->d_sd_depth, 2 * px);
+    if (rc == TSLAM_OK) rc = dev_realloc(h, (void**)&h->d_sd_disp, 2 * px);
+    if (rc == TSLAM_OK) rc = dev_realloc(h, (void**)&h->d_sd_win, 2 * px);
+    if (rc != TSLAM_OK) {
+        h->sd_on = false;
+        return rc;
+    }
+    h->sd_prm = p;
+    h->sd_frames = max_frames;
+    h->sd_w = h->W;
+    h->sd_h = h->H;
+    h->sd_on = true;
+    return TSLAM_OK;
+}
+
+static int stereo_depth_run(tslam_handle* h, StereoDepthArgs a, void* stream) {
+    a.n_disp = h->sd_prm.n_disp;
+    a.uniqueness = h->sd_prm.uniqueness;
+    a.lr_tol = h->sd_prm.lr_tol;
+    a.depth = h->d_sd_depth;
+    a.disp32 = h->d_sd_disp;
+    a.win_left = h->d_sd_win;
+    a.win_right = h->d_sd_win + (size_t)h->sd_frames * h->W * h->H;
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = stream ? (hipStream_t)stream : h->last_stream;
+    HIPCHK(launch_stereo_depth(a, s));
+    h->sd_w = a.W;
+    h->sd_h = a.H;
+    return TSLAM_OK;
+}
+
+int tslam_stereo_depth(tslam_handle* h, int pair, int64_t first_frame, int n_frames, void* stream) {
+    if (!h || pair < 0 || pair >= h->P) return fail(TSLAM_EINVAL, "bad handle or pair");
+    if (!h->sd_on) return fail(TSLAM_ESTATE, "no stereo depth buffers (tslam_stereo_depth_init)");
+    if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_stereo_depth inside a batch");
+    if (n_frames < 0 || n_frames > h->sd_frames) return fail(TSLAM_EINVAL, "n_frames must be 0..max_frames");
+    if (first_frame < h->cur_g0 || first_frame - h->cur_g0 + n_frames > h->cur_n)
+        return fail(TSLAM_EINVAL, "frames must belong to the last batch");
+    BA_FLUSH(h);
+    const uint8_t* pyr = static_cast<const uint8_t*>(h->buf[TSLAM_BUF_PYRAMID].ptr);
+    StereoDepthArgs a{};
+    a.stride = (int64_t)h->C * h->g.pyr_bytes;
+    a.left = pyr + (size_t)(2 * pair) * h->g.pyr_bytes + h->g.pyr_off[0];
+    a.right = a.left + h->g.pyr_bytes;
+    a.ring = h->R;
+    a.first = first_frame;
+    a.W = h->W;
+    a.H = h->H;
+    a.n = n_frames;
+    a.fxb = h->calib[pair].fxb;
+    return stereo_depth_run(h, a, stream);
+}
+
+int tslam_stereo_depth_images(tslam_handle* h, const uint8_t* left, const uint8_t* right, int64_t frame_stride, int width,
+                              int height, double fxb, int n_frames, void* stream) {
+    if (!h || !left || !right) return fail(TSLAM_EINVAL, "bad argument");
+    if (!h->sd_on) return fail(TSLAM_ESTATE, "no stereo depth buffers (tslam_stereo_depth_init)");
+    if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_stereo_depth_images inside a batch");
+    if (n_frames < 0 || n_frames > h->sd_frames) return fail(TSLAM_EINVAL, "n_frames must be 0..max_frames");
+    if (width < 16 || height < 16 || width > h->W || height > h->H)
+        return fail(TSLAM_EINVAL, "width / height must be 16 .. the handle's size");
+    if (n_frames > 1 && frame_stride < (int64_t)width * height) return fail(TSLAM_EINVAL, "frame_stride below one image");
+    if (!(fxb > 0.0)) return fail(TSLAM_EINVAL, "fxb must be > 0");
+    BA_FLUSH(h);
+    StereoDepthArgs a{};
+    a.left = left;
+    a.right = right;
+    a.stride = frame_stride;
+    a.W = width;
+    a.H = height;
+    a.n = n_frames;
+    a.fxb = fxb;
+    return stereo_depth_run(h, a, stream);
+}
+
+int tslam_stereo_depth_buffers(tslam_handle* h, void** depth, void** disp32, int64_t* frame_bytes) {
+    if (!h) return fail(TSLAM_EINVAL, "null handle");
+    if (!h->sd_on) return fail(TSLAM_ESTATE, "no stereo depth buffers (tslam_stereo_depth_init)");
+    if (depth) *depth = h->d_sd_depth;
+    if (disp32) *disp32 = h->d_sd_disp;
+    if (frame_bytes) *frame_bytes = 2LL * h->W * h->H;
+    return TSLAM_OK;
+}
+
+int tslam_stereo_depth_read(tslam_handle* h, int slot, uint16_t* depth, uint16_t* disp32) {
+    if (!h) return fail(TSLAM_EINVAL, "null handle");
+    if (!h->sd_on) return fail(TSLAM_ESTATE, "no stereo depth buffers (tslam_stereo_depth_init)");
+    if (slot < 0 || slot >= h->sd_frames) return fail(TSLAM_EINVAL, "slot out of range");
+    BA_FLUSH(h);
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceSynchronize());
+    const size_t px = (size_t)h->sd_w * h->sd_h;
+    if (depth) HIPCHK(hipMemcpy(depth, h->d_sd_depth + px * slot, 2 * px, hipMemcpyDeviceToHost));
+    if (disp32) HIPCHK(hipMemcpy(disp32, h->d_sd_disp + px * slot, 2 * px, hipMemcpyDeviceToHost));
     return TSLAM_OK;
 }
 

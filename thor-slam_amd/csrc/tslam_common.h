@@ -302,6 +302,23 @@ struct TsdfArgs {
 };
 void launch_tsdf(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev, const TsdfArgs& a, double* poses,
                  hipStream_t s);
+// dense stereo depth (k_stereo_depth.hip): n frames of one rectified pair -> disp32 (1/32 px) and
+// depth (mm), u16 [n][H][W]; win_left / win_right: u8 [n][H][W] winner maps between its two kernels
+struct StereoDepthArgs {
+    const uint8_t* left;       // frame 0's level-0 images (dense rows of W bytes)
+    const uint8_t* right;
+    int64_t stride;            // bytes between frames (ring != 0: between ring slots)
+    int ring;                  // 0: frame f at f * stride; else at ((first + f) % ring) * stride
+    int64_t first;
+    int W, H, n;
+    int n_disp, uniqueness, lr_tol;
+    double fxb;
+    uint16_t* depth;
+    uint16_t* disp32;
+    uint8_t* win_left;
+    uint8_t* win_right;
+};
+hipError_t launch_stereo_depth(const StereoDepthArgs& a, hipStream_t s);
 // dense-map outputs of the TSDF volume (k_dense.hip): marching-cubes mesh, capped exact ESDF
 struct DenseArgs {
     const float* tsdf;

@@ -252,6 +252,16 @@ _SIGNATURES = {
     "tslam_loop_job_poll": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.POINTER(ctypes.c_double)]),
+    "tslam_stereo_depth_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    "tslam_stereo_depth": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "tslam_stereo_depth_images": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                                 ctypes.c_void_p]),
+    "tslam_stereo_depth_buffers": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
+                                                  ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64)]),
+    "tslam_stereo_depth_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "tslam_tsdf_integrate_rect": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                                 ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 
@@ -857,6 +867,52 @@ class Handle:
         _check(self.lib.tslam_tsdf_integrate(self.h, int(pair), ctypes.c_void_p(depth_dev_ptr), int(stride_bytes),
                                              int(n_frames), int(first_frame),
                                              None if poses is None else poses.ctypes.data, ctypes.c_void_p(stream)))
+
+    def tsdf_integrate_rect(self, depth_dev_ptr: int, stride_bytes: int, n_frames: int, first_frame: int = 0,
+                            world_T_cam: np.ndarray | None = None, pair: int = 0, stream: int = 0) -> None:
+        """``tsdf_integrate`` for depth images of the pair's RECTIFIED left camera (``stereo_depth``'s
+        output): no lookup through the raw camera's undistortion table."""
+        poses = None
+        if world_T_cam is not None:
+            poses = np.ascontiguousarray(np.asarray(world_T_cam, dtype=np.float64).reshape(-1, 4, 4))
+        _check(self.lib.tslam_tsdf_integrate_rect(self.h, int(pair), ctypes.c_void_p(depth_dev_ptr), int(stride_bytes),
+                                                  int(n_frames), int(first_frame),
+                                                  None if poses is None else poses.ctypes.data, ctypes.c_void_p(stream)))
+
+    # -- dense stereo depth (thor_slam_amd/stereo_depth.py) ------------------------------------
+    def stereo_depth_init(self, max_frames: int = 1, n_disp: int = 0, uniqueness: int = 10, lr_tol: int = 1) -> None:
+        """Parameters and output slots of the dense stereo matcher (n_disp 0 = the handle's
+        max_disparity)."""
+        prm = (ctypes.c_int32 * 4)(int(n_disp), int(uniqueness), int(lr_tol), 0)
+        _check(self.lib.tslam_stereo_depth_init(self.h, ctypes.addressof(prm), int(max_frames)))
+        self._sd_shape = (self.height, self.width)
+
+    def stereo_depth(self, first_frame: int, n_frames: int, pair: int = 0, stream: int = 0) -> None:
+        """Depth of ``pair``'s frames first_frame.. of the last batch into slots 0..n_frames-1."""
+        _check(self.lib.tslam_stereo_depth(self.h, int(pair), int(first_frame), int(n_frames), ctypes.c_void_p(stream)))
+        self._sd_shape = (self.height, self.width)
+
+    def stereo_depth_images(self, left_dev_ptr: int, right_dev_ptr: int, frame_stride: int, width: int, height: int,
+                            fxb: float, n_frames: int, stream: int = 0) -> None:
+        """The matcher on caller-supplied rectified device images (u8, dense rows, frames
+        ``frame_stride`` bytes apart); outputs dense [n_frames][height][width]."""
+        _check(self.lib.tslam_stereo_depth_images(self.h, ctypes.c_void_p(left_dev_ptr), ctypes.c_void_p(right_dev_ptr),
+                                                  int(frame_stride), int(width), int(height), float(fxb), int(n_frames),
+                                                  ctypes.c_void_p(stream)))
+        self._sd_shape = (int(height), int(width))
+
+    def stereo_depth_buffers(self) -> tuple[int, int, int]:
+        """(depth device pointer, disp32 device pointer, bytes of one full-size slot)."""
+        d, q, b = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        _check(self.lib.tslam_stereo_depth_buffers(self.h, ctypes.byref(d), ctypes.byref(q), ctypes.byref(b)))
+        return int(d.value or 0), int(q.value or 0), int(b.value)
+
+    def stereo_depth_read(self, slot: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """(depth u16 mm, disp32 u16 in 1/32 px) of one slot of the last call (synchronises)."""
+        depth = np.zeros(self._sd_shape, dtype=np.uint16)
+        disp = np.zeros(self._sd_shape, dtype=np.uint16)
+        _check(self.lib.tslam_stereo_depth_read(self.h, int(slot), depth.ctypes.data, disp.ctypes.data))
+        return depth, disp
 
     def tsdf_read(self) -> tuple[np.ndarray, np.ndarray]:
         """(tsdf, weight) as f32 [nz][ny][nx] (synchronises)."""

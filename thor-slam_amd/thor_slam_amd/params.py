@@ -11,6 +11,7 @@ from __future__ import annotations
 from dataclasses import dataclass
 
 from .slam.interface import SlamConfig
+from .stereo_depth import check_params as check_stereo_depth_params
 
 # Upper bounds baked into the kernels (checked on the host before any launch).
 MAX_WIDTH = 2047
@@ -135,6 +136,14 @@ class HipSlamConfig(SlamConfig):
     esdf_integrator_max_site_distance_vox: float = 1.0
     esdf_slice_min_height: float = -0.5
     esdf_slice_max_height: float = 0.5
+    # dense stereo depth (thor_slam_amd/stereo_depth.py): on a stereo rig, pair 0's depth image is
+    # computed on the device from the rectified images (candidate disparities 0 .. max_disparity - 1)
+    # and feeds dense_map as an RGB-D camera's depth does (no colour layer: the images are gray, so
+    # dense_color is ignored).  Frames g with g % stereo_depth_interval == 0 are matched and integrated.
+    stereo_depth: bool = False
+    stereo_depth_uniqueness: int = 10   # percent: best cost <= (100 - u) % of the best non-neighbour
+    stereo_depth_lr_tol: int = 1        # px, left-right consistency
+    stereo_depth_interval: int = 1
     # pipeline
     batch_size: int = 1             # frames per submission
     sync: bool = False              # wait for every batch before process_frames returns (latency mode)
@@ -160,9 +169,17 @@ class HipSlamConfig(SlamConfig):
             raise ValueError("batch_size must be >= 1")
         if self.imu_accel and self.imu_fusion is False:
             raise ValueError("imu_accel needs IMU fusion (imu_fusion True or None)")
+        if self.stereo_depth:
+            if self.rgbd:
+                raise ValueError("stereo_depth is for stereo rigs (rgbd=True already has depth)")
+            if self.devices:
+                raise ValueError("stereo_depth does not run on a sharded rig (devices)")
+        check_stereo_depth_params(0, self.stereo_depth_uniqueness, self.stereo_depth_lr_tol)
+        if self.stereo_depth_interval < 1:
+            raise ValueError("stereo_depth_interval must be >= 1")
         if self.dense_map:
-            if not self.rgbd:
-                raise ValueError("dense_map needs rgbd=True (depth input)")
+            if not (self.rgbd or self.stereo_depth):
+                raise ValueError("dense_map needs depth: rgbd=True (depth input) or stereo_depth=True (stereo rig)")
             if not (self.voxel_size > 0 and self.tsdf_integrator_max_integration_distance_m > 0
                     and self.tsdf_integrator_truncation_distance_vox > 0 and self.tsdf_max_weight >= 1):
                 raise ValueError("voxel_size, integration distance, truncation must be > 0, max weight >= 1")

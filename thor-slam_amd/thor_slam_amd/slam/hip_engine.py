@@ -26,7 +26,10 @@ published pose is the rig's front end carried by the body correction ``B_ba(kf) 
 and ``get_map`` returns the body keyframes and every pair's landmarks.
 With ``dense_map`` (RGB-D input) every batch's depth of pair 0 is integrated into a dense TSDF
 volume on the device with the batch's tracked poses (nvblox's role in the reference pipeline,
-``scripts/run_pipeline.py:218-256``); ``get_dense_map`` returns it.
+``scripts/run_pipeline.py:218-256``); ``get_dense_map`` returns it.  On a stereo rig
+``stereo_depth`` supplies that depth: pair 0's rectified images go through the dense stereo matcher
+(``thor_slam_amd/stereo_depth.py``) every ``stereo_depth_interval``-th frame, in the same
+synchronous branch; ``get_depth_image`` returns the newest depth image.
 With ``HipSlamConfig(devices=[d0, d1, ...])`` the rig is sharded one camera stream per GPU from
 this one process (cuVSLAM's multicam mode, launch/thor_visual_slam.launch.py:49,81):
 one handle per device, driven by the library as one sharded rig (``tslam_group_*``: an RCCL clique
@@ -448,6 +451,7 @@ class HipSlamEngine(SlamEngine):
         self._loop: _LoopGraph | None = None     # set up by initialize() when loop closure is on
         self._in_flight = 0                       # batches submitted, not yet published
         self._shard: dict | None = None           # sharded rig (config.devices): handles, group, inputs
+        self._sd_last: tuple | None = None        # (slot, timestamp) of the newest stereo depth image
 
     # ------------------------------------------------------------------------------------------
     def initialize(self, calibration: RigCalibration, config: SlamConfig | None = None) -> None:
@@ -509,11 +513,15 @@ class HipSlamEngine(SlamEngine):
             if len(self._pairs) > 1 and self._shard is None:   # the rig's body motion, on the device from all pairs
                 self._handle.set_rig(self._base_T_rects)
             if cfg.dense_map:
-                if cfg.dense_color:
+                if self._dense_color:
                     self._handle.tsdf_color(True)
                 self._handle.tsdf_init(cfg.tsdf_origin, cfg.tsdf_dims, cfg.voxel_size,
                                        cfg.tsdf_integrator_truncation_distance_vox,
                                        cfg.tsdf_integrator_max_integration_distance_m, cfg.tsdf_max_weight)
+                if cfg.stereo_depth:   # a stereo rig: pair 0's depth comes from the dense matcher
+                    self._handle.stereo_depth_init(max_frames=cfg.batch_size, uniqueness=cfg.stereo_depth_uniqueness,
+                                                   lr_tol=cfg.stereo_depth_lr_tol)
+            self._sd_last = None   # (slot, timestamp) of the newest stereo depth image
             self._loop = None
             if cfg.enable_loop_closure and cfg.devices and cfg.rgbd:
                 # rank 0's ring holds only its own cameras' features (no state gather): no rig-wide
@@ -706,7 +714,7 @@ class HipSlamEngine(SlamEngine):
             stream = torch.cuda.current_stream(self._device)
             self._dev_images[:n].copy_(self._host_images[:n], non_blocking=True)
             self._handle.submit(self._dev_images.data_ptr(), n, stream.cuda_stream)
-            self._integrate_depth(self._dev_images.data_ptr(), n, stream.cuda_stream)
+            self._integrate_depth(self._dev_images.data_ptr(), n, stream.cuda_stream, stamps=stamps)
             self._staged, self._staged_imu = [], []
             self._prev_stamp = stamps[-1]
             self._publish(self._read(n), stamps, self._handle.frames_done - n)
@@ -918,27 +926,59 @@ class HipSlamEngine(SlamEngine):
         s = stream if stream is not None else self._torch.cuda.current_stream(self._device)
         self.flush()
         self._handle.submit(images.data_ptr(), n, s.cuda_stream)
-        self._integrate_depth(images.data_ptr(), n, s.cuda_stream)
+        self._integrate_depth(images.data_ptr(), n, s.cuda_stream, stamps=timestamps)
         res = self._read(n)
         self._publish(res, timestamps or [float(i) for i in range(n)], self._handle.frames_done - n)
         return res
 
     # -- RGB-D dense mapping ----------------------------------------------
-    def _integrate_depth(self, records_ptr: int, n: int, stream: int, cams_per_frame: int | None = None) -> None:
+    @property
+    def _dense_color(self) -> bool:
+        """The colour layer needs colour input: a stereo rig's images are gray, so ``dense_color``
+        is ignored with ``stereo_depth``."""
+        return self._config.dense_color and not self._config.stereo_depth
+
+    def _integrate_depth(self, records_ptr: int, n: int, stream: int, cams_per_frame: int | None = None,
+                         stamps: list | None = None) -> None:
         """The batch's depth images of pair 0 into the TSDF volume, with the batch's device-resident
         tracked poses (untracked frames are skipped), on the batch's stream.  ``cams_per_frame``: the
-        records per frame of the buffer (a sharded rig: rank 0's cameras, pair 0 first)."""
+        records per frame of the buffer (a sharded rig: rank 0's cameras, pair 0 first).  With
+        ``stereo_depth`` the depth of the batch's frames g with g % stereo_depth_interval == 0 is
+        first computed from pair 0's rectified images (k_stereo_depth.hip), in the rectified camera."""
         if not self._config.dense_map:
+            return
+        if self._config.stereo_depth:
+            g0 = self._handle.frames_done - n
+            every = self._config.stereo_depth_interval
+            depth_ptr, _, frame_bytes = self._handle.stereo_depth_buffers()
+            # one launch per run of consecutive frames (the whole batch at interval 1)
+            runs = [(g0, n)] if every == 1 else [(g, 1) for g in range(g0, g0 + n) if g % every == 0]
+            for g, m in runs:
+                self._handle.stereo_depth(g, m, pair=0, stream=stream)
+                self._handle.tsdf_integrate_rect(depth_ptr, frame_bytes, m, first_frame=g, pair=0, stream=stream)
+                self._sd_last = (m - 1, None if stamps is None else float(stamps[g + m - 1 - g0]))
             return
         r = self._rects[0]
         hw = r.width * r.height
         stride = 5 * hw * (cams_per_frame or len(self._pairs))
-        if self._config.dense_color:   # the record's BGR part with its depth part
+        if self._dense_color:   # the record's BGR part with its depth part
             self._handle.tsdf_integrate_rgbd(records_ptr, records_ptr + 3 * hw, stride, n,
                                              first_frame=self._handle.frames_done - n, pair=0, stream=stream)
         else:
             self._handle.tsdf_integrate(records_ptr + 3 * hw, stride, n,
                                         first_frame=self._handle.frames_done - n, pair=0, stream=stream)
+
+    def get_depth_image(self) -> tuple | None:
+        """(depth u16 [H][W] in mm of pair 0's rectified left camera, timestamp) of the newest frame
+        the dense stereo matcher processed, or None (``stereo_depth`` with ``dense_map`` only).
+        Synchronises."""
+        if self._handle is None or not (self._config.stereo_depth and self._config.dense_map):
+            return None
+        self.flush()
+        if self._sd_last is None:
+            return None
+        slot, stamp = self._sd_last
+        return self._handle.stereo_depth_read(slot)[0], stamp
 
     def get_dense_map(self) -> dict | None:
         """The TSDF volume (nvblox-shaped): ``tsdf`` / ``weight`` f32 [nz][ny][nx] (metres of
@@ -952,7 +992,7 @@ class HipSlamEngine(SlamEngine):
         self.flush()
         tsdf, weight = self._handle.tsdf_read()
         out = {}
-        if cfg.dense_color:
+        if self._dense_color:
             out["color"], out["color_weight"] = self._handle.tsdf_read_color()
         return {**out, "tsdf": tsdf, "weight": weight, "origin": np.array(cfg.tsdf_origin, dtype=np.float64),
                 "voxel_size": float(cfg.voxel_size),
@@ -967,7 +1007,7 @@ class HipSlamEngine(SlamEngine):
         if not cfg.dense_map or self._handle is None:
             return None
         self.flush()
-        if cfg.dense_color:
+        if self._dense_color:
             tris, cols = self._handle.mesh(cfg.mesh_integrator_min_weight, colors=True)
             return {"triangles": tris, "colors": cols, "world_T_volume": self._map_offset @ self._base_T_rect}
         return {"triangles": self._handle.mesh(cfg.mesh_integrator_min_weight),
@@ -1365,6 +1405,7 @@ class HipSlamEngine(SlamEngine):
         self._imu_seq = 0
         self._kf_imu = None
         self._kf_ine = None
+        self._sd_last = None
         if self._imu is not None:
             self._imu.reset()
         self._keyframe_poses = []

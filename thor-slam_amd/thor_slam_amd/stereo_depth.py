@@ -1,0 +1,53 @@
+"""Dense stereo depth on the device: a depth image from a rectified stereo pair, so that a stereo
+rig feeds the TSDF volume the way an RGB-D camera does.  The reference needs no such step because
+its cameras compute stereo depth themselves (DepthAI on-device StereoDepth)
+and hand nvblox a depth image.  The rules below are the spec, in integers so that the device
+(``csrc/k_stereo_depth.hip``) is bit-exact with an independent NumPy restatement
+(``tests/ref_stereo_depth.py``; the product does not import it).
+
+Inputs: the rectified level-0 images L, R (u8 [H][W]) of one pair; fxb = fx * baseline of the pair.
+Parameters: n_disp D (candidates 0..D-1, 4..256), uniqueness u (0..99), lr_tol (px, >= 0).
+
+1. Census 7x7 of L and R: 48 bits per pixel, a bit is 1 iff the neighbour is strictly less than
+   the centre; neighbours outside the image read the replicated border pixel.
+2. Cost C(d, y, x) = popcount(censusL(y, x) ^ censusR(y, x - d)) for x >= d, the constant 48 for
+   x < d.
+3. Aggregation A(d, y, x) = sum of C(d, ., .) over the 5x5 window centred on (y, x), window
+   coordinates clamped to the image (replicated border of each d plane); A <= 1200.
+4. Left winner: d1 = the smallest d minimising A(d, y, x), m1 = that minimum, m2 = the minimum of A
+   over all d with |d - d1| > 1 (2^30 if there is none).
+5. Right winner, from the same volume: dR(y, xr) = the smallest d minimising A(d, y, xr + d) over d
+   with xr + d < W.
+6. A pixel is valid iff d1 >= 1, m1 * 100 <= m2 * (100 - u), x - d1 >= 0 and
+   |dR(y, x - d1) - d1| <= lr_tol.
+7. Sub-pixel in 1/32 px: if 1 <= d1 <= D - 2, with c0 = A(d1 - 1, y, x), c2 = A(d1 + 1, y, x) and
+   den = c0 - 2 m1 + c2 > 0: off = floor((32 (c0 - c2) + den) / (2 den)) (a true floor, so
+   off in [-16, 16]); otherwise off = 0.  disp32 = 32 d1 + off as u16, 0 where invalid.
+8. Depth: mm = floor((fxb * 32000.0) / (double) disp32 + 0.5) (f64: one multiply, one divide, one
+   add, in that order); depth = mm as u16, or 0 where the pixel is invalid or mm > 65535.
+
+Out of scope: semi-global path aggregation, median and speckle filters, matching on a coarser
+pyramid level, a colour layer from the gray images; the engine integrates pair 0 only (the C ABI
+takes any pair) and does not run on sharded rigs.
+"""
+
+from __future__ import annotations
+
+CENSUS_RADIUS = 3      # 7x7 window, 48 bits
+BOX_RADIUS = 2         # 5x5 aggregation
+COST_OUTSIDE = 48      # C(d, y, x) for x < d
+SUBPIXEL = 32          # disparity units per pixel
+NO_SECOND_MINIMUM = 1 << 30
+
+N_DISP_MIN, N_DISP_MAX = 4, 256
+DEFAULT_UNIQUENESS = 10
+DEFAULT_LR_TOL = 1
+
+
+def check_params(n_disp: int, uniqueness: int, lr_tol: int) -> None:
+    if n_disp != 0 and not N_DISP_MIN <= n_disp <= N_DISP_MAX:
+        raise ValueError(f"n_disp must be 0 (the handle's max_disparity) or in [{N_DISP_MIN}, {N_DISP_MAX}]")
+    if not 0 <= uniqueness <= 99:
+        raise ValueError("uniqueness must be in [0, 99]")
+    if lr_tol < 0:
+        raise ValueError("lr_tol must be >= 0")

@@ -1,0 +1,109 @@
+"""Time the dense stereo matcher (tslam_stereo_depth, k_stereo_depth.hip) on resident data.
+
+    python tools/stereo_depth_probe.py [--frames 64] [--disp 128] [--reps 10] [--out profiles/stereo_depth_c2.json]
+
+C2 geometry by default (640x400, one pair, D = 128, 64 frames resident in the ring).  One batch is
+tracked first so the ring holds rectified images; after a warm-up launch the matcher runs `reps`
+times between two HIP events on the launch stream.  For the cost relative to tracking the same run
+times k_detect alone (inside a batch, also between events) over the same frames.  The bytes per
+frame are what the algorithm must move (both images read once, depth + disp32 written, the two u8
+winner maps written and read once); (x, d) cells = W * H * D per frame.  Needs the GPU: there is
+no fallback.
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[1]
+for p in (ROOT, ROOT / "thor-slam_amd"):
+    sys.path.insert(0, str(p))
+
+HBM_PEAK_TBS = 8.0
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=64)
+    ap.add_argument("--disp", type=int, default=128)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--width", type=int, default=640)
+    ap.add_argument("--height", type=int, default=400)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    import torch
+
+    from thor_slam_amd._lib import Handle
+    from thor_slam_amd.calib import extract_cameras, stereo_pairs, stereo_rectify
+    from thor_slam_amd.camera.rig import CameraRig
+    from thor_slam_amd.params import HipSlamConfig
+    from thor_slam_amd.synthetic import SyntheticStereoSource
+
+    assert torch.cuda.is_available(), "the probe measures on the GPU"
+    W, H, B, D = args.width, args.height, args.frames, args.disp
+    src = SyntheticStereoSource(seed=0, width=W, height=H)
+    cams = extract_cameras(CameraRig([src]).calibration, 2)
+    (li, ri), = stereo_pairs(cams)
+    rect = stereo_rectify(cams[li], cams[ri])
+    uniq = src.render_stereo_sequence(8)
+    frames = uniq[[i % 8 for i in range(B)]]
+    dev = torch.from_numpy(frames).cuda()
+    h = Handle([rect], HipSlamConfig(), max_batch=B)
+    stream = torch.cuda.current_stream()
+    s = stream.cuda_stream
+    h.submit(dev.data_ptr(), B, s)
+    torch.cuda.synchronize()
+    h.stereo_depth_init(max_frames=B, n_disp=D)
+
+    def timed(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(reps):
+            fn()
+        e1.record(stream)
+        torch.cuda.synchronize()
+        return 1000.0 * e0.elapsed_time(e1) / reps   # us per call
+
+    run = lambda: h.stereo_depth(0, B, pair=0, stream=s)   # noqa: E731
+    timed(run, 2)                                          # warm-up (code object, attribute call)
+    trials = [timed(run, args.reps) for _ in range(3)]
+    us_batch = min(trials)
+    depth, disp32 = h.stereo_depth_read(B - 1)
+    valid = float((depth > 0).mean())
+
+    h.begin_batch(dev.data_ptr(), B)
+    h.run_kernel("rectify_pyramid", s)
+    timed(lambda: h.run_kernel("detect", s), 2)
+    det_trials = [timed(lambda: h.run_kernel("detect", s), args.reps) for _ in range(3)]
+    h.end_batch()
+    h.close()
+
+    us_frame = us_batch / B
+    bytes_frame = 2 * W * H + 2 * 2 * W * H + 2 * 2 * W * H   # images + u16 outputs + u8 winner maps (write, read)
+    out = {
+        "what": "tslam_stereo_depth, HIP events around %d back-to-back calls, best of 3 trials" % args.reps,
+        "width": W, "height": H, "n_disp": D, "frames": B,
+        "us_per_batch_trials": [round(t, 1) for t in trials],
+        "us_per_frame": round(us_frame, 2),
+        "bytes_per_frame": bytes_frame,
+        "achieved_GBps": round(bytes_frame / us_frame / 1e3, 2),
+        "share_of_8TBps_peak": round(bytes_frame / us_frame / 1e6 / HBM_PEAK_TBS, 5),
+        "cells_per_frame": W * H * D,
+        "cells_per_second": round(W * H * D / us_frame * 1e6, 0),
+        "valid_fraction_last_frame": round(valid, 4),
+        "k_detect_us_per_batch_trials": [round(t, 1) for t in det_trials],
+        "k_detect_us_per_frame_both_cameras": round(min(det_trials) / B, 3),
+        "stereo_depth_over_k_detect": round(us_batch / min(det_trials), 1),
+    }
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
