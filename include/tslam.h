@@ -101,7 +101,8 @@ typedef struct {
                                      1 exhaustive, 2 bounded; never changes results             */
     int32_t refine_block;         /* k_refine threads per frame: 0 auto (128 from 512 frames per
                                      launch), 128 or 256; never changes results                  */
-    int32_t reserved0;            /* 0                                                        */
+    int32_t match_refine;         /* stereo + temporal sub-pixel refinement of a stereo frame: 0 auto
+                                     (one fused kernel), 1 split (two kernels); never changes results */
 } tslam_params;
 
 /* One raw camera as IsaacRosAdapter publishes it (camera_info K/D + the rig extrinsics,

@@ -390,21 +390,156 @@ __device__ __forceinline__ void row11(const uint8_t* img, int W, int y, int x0, 
     w[2] = __builtin_amdgcn_alignbyte(d3, d2, sh) & 0x00FFFFFFu;
 }
 
+// One staged LDS row (16 bytes): the 11 patch bytes of row `y` from column `x0`, the rest zero ...
+__device__ __forceinline__ uint4 stage_row11(const uint8_t* img, int W, int y, int x0) {
+    uint32_t w3[3];
+    row11(img, W, y, x0, w3);
+    return uint4{w3[0], w3[1], w3[2], 0u};
+}
+
+// ... or the 15 window bytes (byte 15 zero): 5 aligned dwords `d` + v_alignbyte by the address's low bits
+__device__ __forceinline__ uint4 align_row15(const uint32_t* d, uint32_t sh) {
+    return uint4{__builtin_amdgcn_alignbyte(d[1], d[0], sh), __builtin_amdgcn_alignbyte(d[2], d[1], sh),
+                 __builtin_amdgcn_alignbyte(d[3], d[2], sh), __builtin_amdgcn_alignbyte(d[4], d[3], sh) & 0x00FFFFFFu};
+}
+__device__ __forceinline__ uint4 stage_row15(const uint8_t* img, int W, int y, int x0) {
+    const uint8_t* a = img + (size_t)y * W + x0;
+    const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3u);
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(a - sh);
+    const uint32_t d[5] = {q[0], q[1], q[2], q[3], q[4]};
+    return align_row15(d, sh);
+}
+
+// Bytes kx .. kx+10 (kx = 0..4) of a staged 15-byte row as three dwords (byte 12 zeroed).
+// kx == 4: start one word later with no byte shift (the 4th word is then unused)
+__device__ __forceinline__ void shift_row11(const uint4* row, int kx, uint32_t* w) {
+    const uint32_t* wb = reinterpret_cast<const uint32_t*>(row);
+    const int kh = kx >> 2;
+    const uint32_t sh = (uint32_t)(kx & 3);
+    const uint32_t d0 = wb[kh], d1 = wb[kh + 1], d2 = wb[kh + 2], d3 = wb[3 - kh];
+    w[0] = __builtin_amdgcn_alignbyte(d1, d0, sh);
+    w[1] = __builtin_amdgcn_alignbyte(d2, d1, sh);
+    w[2] = __builtin_amdgcn_alignbyte(d3, d2, sh) & 0x00FFFFFFu;
+}
+
+__device__ __forceinline__ uint32_t sad_row11(const uint32_t* a, const uint32_t* w, uint32_t s) {
+    s = __builtin_amdgcn_sad_u8(a[0], w[0], s);
+    s = __builtin_amdgcn_sad_u8(a[1], w[1], s);
+    return __builtin_amdgcn_sad_u8(a[2], w[2], s);
+}
+
+// Stereo SAD of one offset: the 11x11 left patch against bytes kx .. kx+10 of the 11 staged right
+// window rows (right patch centred at xr + kx - 2).  The left rows are staged patch rows (ASH < 0)
+// or rows of the staged 15x15 temporal window, whose bytes ASH .. ASH+10 are the patch row.
+template <int ASH>
+__device__ __forceinline__ uint32_t stereo_sad(const uint4* a, const uint4* b, int kx) {
+    uint32_t s = 0;
+#pragma unroll
+    for (int dy = 0; dy < 11; ++dy) {
+        uint32_t la[3], w[3];
+        if (ASH < 0) {
+            const uint4 ra = a[dy];
+            la[0] = ra.x, la[1] = ra.y, la[2] = ra.z;
+        } else {
+            shift_row11(a + dy, ASH, la);
+        }
+        shift_row11(b + dy, kx, w);
+        s = sad_row11(la, w, s);
+    }
+    return s;
+}
+
+// The stereo result of one live query: match j (or -1) and, from the 5 costs and the first
+// minimum ks, the disparity (NaN: rejected, minimum at the range's edge, or not positive).
+__device__ __forceinline__ void stereo_store(const BatchCtx& c, size_t out, int j, int l, int qx, int xr, int ks,
+                                             const int* cost) {
+    double d0 = __builtin_nan("");
+    if (j >= 0 && ks > 0 && ks < 4) {
+        const double delta = parabola(cost[ks - 1], cost[ks], cost[ks + 1]);
+        const double sc = (double)(1 << l);
+        const double v = ((double)qx - ((double)(xr + (ks - TS_SAD_RANGE)) + delta)) * sc;
+        if (v > 0.0) d0 = v;
+    }
+    c.stereo[out] = j;
+    c.disp[out] = d0;
+}
+
+// Temporal SAD of the 5 offsets (kx, ky = 0..4) of column shift kx: each of the 15 staged window
+// rows `b` is realigned once (its 11 bytes from kx on) and serves every ky it meets (patch row
+// dy = r - ky of `a`); the sums are integers, so the costs equal a per-offset loop's
+#define TS_RT_AROWS 11
+#define TS_RT_BROWS 15
+__device__ __forceinline__ void temporal_sad(const uint4* a, const uint4* b, int kx, uint32_t* s) {
+#pragma unroll
+    for (int ky = 0; ky < 5; ++ky) s[ky] = 0u;
+#pragma unroll
+    for (int r = 0; r < TS_RT_BROWS; ++r) {
+        uint32_t w[3];
+        shift_row11(b + r, kx, w);
+#pragma unroll
+        for (int ky = 0; ky < 5; ++ky) {
+            const int dy = r - ky;
+            if (dy < 0 || dy >= TS_RT_AROWS) continue;   // compile-time
+            const uint4 ra = a[dy];
+            const uint32_t la[3] = {ra.x, ra.y, ra.z};
+            s[ky] = sad_row11(la, w, s[ky]);
+        }
+    }
+}
+
+// The temporal result of one live query from the 25 costs and the first minimum `a` (ky * 5 + kx):
+// (u, v) at t in level-0 pixels, NaN when rejected or the minimum lies on the search border.
+__device__ __forceinline__ void temporal_store(double* out_uv, int j, int l, int qx, int qy, int a, const int* cq) {
+    double u = __builtin_nan(""), v = u;
+    if (j >= 0) {
+        const int c0 = cq[a];
+        const int cl = cq[max(a - 1, 0)], cr = cq[min(a + 1, 24)];
+        const int cu = cq[max(a - 5, 0)], cd = cq[min(a + 5, 24)];
+        const int ky = a / 5, kx = a % 5;
+        if (kx > 0 && kx < 4 && ky > 0 && ky < 4) {
+            const double ddx = parabola(cl, c0, cr);
+            const double ddy = parabola(cu, c0, cd);
+            const double sc = (double)(1 << l);
+            u = (((double)(qx + (kx - TS_SAD_RANGE)) + ddx) + 0.5) * sc - 0.5;
+            v = (((double)(qy + (ky - TS_SAD_RANGE)) + ddy) + 0.5) * sc - 0.5;
+        }
+    }
+    out_uv[0] = u;
+    out_uv[1] = v;
+}
+
 // The match of the query at y-sorted position `pos` (keypoint qi): k_match stores (qbest, qsecond)
 // by position, so they load beside the query's record, and the train side's best query and the
 // train's keypoint word {x | y << 16} (image base tkb) load together once the best train j is
 // known — two dependent rounds instead of three.  Returns j when the match passes max distance,
 // ratio and the mutual check (and `ok`), else -1.
+// The lookup comes in its two load rounds and the test (k_refine_pair issues each round for both
+// modes at once); the test's terms are all evaluated (&, not &&), so that no load sinks into a
+// branch behind another load's wait.
+struct MatchRef {
+    uint32_t qb, sd, tb;
+    int j;
+};
+__device__ __forceinline__ void match_query(const BatchCtx& c, size_t mbase, int pos, MatchRef* m) {
+    m->qb = c.qbest[mbase + pos];
+    m->sd = c.qsecond[mbase + pos];
+    m->j = m->qb == 0xFFFFFFFFu ? 0 : (int)(m->qb & 0xFFFF);
+}
+__device__ __forceinline__ void match_train(const BatchCtx& c, size_t mbase, size_t tkb, MatchRef* m, uint32_t* tkp) {
+    m->tb = c.tbest[mbase + m->j];
+    *tkp = c.kps[(tkb + m->j) * 2];
+}
+__device__ __forceinline__ int match_accept(const BatchCtx& c, const MatchRef& m, int qi, bool ok) {
+    const int bd = (int)(m.qb >> 16);
+    return ((int)ok & (int)(m.qb != 0xFFFFFFFFu) & (int)(bd <= c.mp.max_hamming) &
+            (int)(bd * 100 < c.mp.ratio_pct * (int)m.sd) & (int)((int)(m.tb & 0xFFFF) == qi)) ? m.j : -1;
+}
 __device__ __forceinline__ int match_lookup(const BatchCtx& c, size_t mbase, int pos, int qi, bool ok, size_t tkb,
                                             uint32_t* tkp) {
-    const uint32_t qb = c.qbest[mbase + pos];
-    const uint32_t sd = c.qsecond[mbase + pos];
-    const int j = qb == 0xFFFFFFFFu ? 0 : (int)(qb & 0xFFFF);
-    const uint32_t tb = c.tbest[mbase + j];
-    *tkp = c.kps[(tkb + j) * 2];
-    const int bd = (int)(qb >> 16);
-    return (ok && qb != 0xFFFFFFFFu && bd <= c.mp.max_hamming && bd * 100 < c.mp.ratio_pct * (int)sd &&
-            (int)(tb & 0xFFFF) == qi) ? j : -1;
+    MatchRef m;
+    match_query(c, mbase, pos, &m);
+    match_train(c, mbase, tkb, &m, tkp);
+    return match_accept(c, m, qi, ok);
 }
 
 // Stereo refinement (A6b): validity + disparity by 5-offset SAD + parabola.  Eight queries per
@@ -443,11 +578,6 @@ __global__ __launch_bounds__(256) void k_refine_stereo(BatchCtx c) {
         qxy = rec.x;
         j = match_lookup(c, mbase, pos, qi, rec.w != 0, ((size_t)slot * c.C + qcam + 1) * K, &tkp);
     }
-    const double nanv = __builtin_nan("");
-    if (live && sub == 0 && j < 0) {
-        c.stereo[((size_t)slot * c.P + p) * K + qi] = -1;
-        c.disp[((size_t)slot * c.P + p) * K + qi] = nanv;
-    }
     int qx = 0, xr = 0;
     if (j >= 0) {
         const int W = c.g.W[l];
@@ -457,59 +587,23 @@ __global__ __launch_bounds__(256) void k_refine_stereo(BatchCtx c) {
         const uint8_t* Lp = c.pyr + ((size_t)slot * c.C + qcam) * c.g.pyr_bytes + c.g.pyr_off[l];
         const uint8_t* Rp = c.pyr + ((size_t)slot * c.C + qcam + 1) * c.g.pyr_bytes + c.g.pyr_off[l];
         for (int hl = sub; hl < 22; hl += 8) {
-            if (hl < 11) {
-                uint32_t w3[3];
-                row11(Lp, W, qy - TS_SAD_HALF + hl, qx - TS_SAD_HALF, w3);
-                s_a[qslot][hl] = uint4{w3[0], w3[1], w3[2], 0u};
-            } else {
-                const int r = hl - 11;
-                const uint8_t* a = Rp + (size_t)(qy - TS_SAD_HALF + r) * W + (xr - TS_SAD_HALF - TS_SAD_RANGE);
-                const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3u);
-                const uint32_t* q = reinterpret_cast<const uint32_t*>(a - sh);
-                const uint32_t d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3], d4 = q[4];
-                s_b[qslot][r] = uint4{__builtin_amdgcn_alignbyte(d1, d0, sh), __builtin_amdgcn_alignbyte(d2, d1, sh),
-                                      __builtin_amdgcn_alignbyte(d3, d2, sh), __builtin_amdgcn_alignbyte(d4, d3, sh) & 0x00FFFFFFu};
-            }
+            if (hl < 11)
+                s_a[qslot][hl] = stage_row11(Lp, W, qy - TS_SAD_HALF + hl, qx - TS_SAD_HALF);
+            else
+                s_b[qslot][hl - 11] = stage_row15(Rp, W, qy - TS_SAD_HALF + hl - 11, xr - TS_SAD_HALF - TS_SAD_RANGE);
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // staged rows before the reads (own wave)
     uint32_t key = 0xFFFFFFFFu;
     if (j >= 0 && sub < 5) {
-        const int kx = sub;   // window bytes kx .. kx+10: right patch centred at xr + kx - 2
-        // kx == 4: start one word later with no byte shift (the 4th word is then unused)
-        const int kh = kx >> 2;
-        const uint32_t sh = (uint32_t)(kx & 3);
-        const uint32_t* wb = reinterpret_cast<const uint32_t*>(&s_b[qslot][0]);
-        uint32_t s = 0;
-#pragma unroll
-        for (int dy = 0; dy < 11; ++dy) {
-            const uint4 ra = s_a[qslot][dy];
-            const uint32_t d0 = wb[4 * dy + kh], d1 = wb[4 * dy + kh + 1], d2 = wb[4 * dy + kh + 2], d3 = wb[4 * dy + 3 - kh];
-            const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, sh);
-            const uint32_t w1 = __builtin_amdgcn_alignbyte(d2, d1, sh);
-            const uint32_t w2 = __builtin_amdgcn_alignbyte(d3, d2, sh) & 0x00FFFFFFu;
-            s = __builtin_amdgcn_sad_u8(ra.x, w0, s);
-            s = __builtin_amdgcn_sad_u8(ra.y, w1, s);
-            s = __builtin_amdgcn_sad_u8(ra.z, w2, s);
-        }
+        const uint32_t s = stereo_sad<-1>(s_a[qslot], s_b[qslot], sub);
         s_cost[qslot][sub] = (int)s;
         key = (s << 5) | (uint32_t)sub;
     }
 #pragma unroll
     for (int m = 1; m < 8; m <<= 1) key = min(key, (uint32_t)__shfl_xor((int)key, m, 64));
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // costs of the 5 lanes before the reads
-    if (j >= 0 && sub == 0) {
-        const int ks = (int)(key & 31u);
-        double d0 = nanv;
-        if (ks > 0 && ks < 4) {
-            const double delta = parabola(s_cost[qslot][ks - 1], s_cost[qslot][ks], s_cost[qslot][ks + 1]);
-            const double sc = (double)(1 << l);
-            const double v = ((double)qx - ((double)(xr + (ks - TS_SAD_RANGE)) + delta)) * sc;
-            if (v > 0.0) d0 = v;
-        }
-        c.stereo[((size_t)slot * c.P + p) * K + qi] = j;
-        c.disp[((size_t)slot * c.P + p) * K + qi] = d0;
-    }
+    if (live && sub == 0) stereo_store(c, ((size_t)slot * c.P + p) * K + qi, j, l, qx, xr, (int)(key & 31u), s_cost[qslot]);
 }
 
 // Temporal refinement (A7a): validity + position by 5x5 SAD search + 2-D parabola.  Eight queries
@@ -519,8 +613,6 @@ __global__ __launch_bounds__(256) void k_refine_stereo(BatchCtx c) {
 // rows s, s+8, .. of the 26), rows padded to 16 bytes and read back as ds_read_b128; sub-lane s
 // scores offsets s, s+8, s+16, s+24 of the 25; the first minimum is an xor-shuffle over the 8
 // lanes.  grid xcd_grid(n*P, ceil(K/32)), block 256.
-#define TS_RT_AROWS 11
-#define TS_RT_BROWS 15
 #define TS_RT_QPB 32   // queries per block
 __global__ __launch_bounds__(256) void k_refine_temporal(BatchCtx c) {
     TS_BACK_PRIO;
@@ -553,12 +645,7 @@ __global__ __launch_bounds__(256) void k_refine_temporal(BatchCtx c) {
     }
     int32_t* out_idx = c.temporal + ((size_t)slot * c.P + p) * K;
     double* out_uv = c.tuv + (((size_t)f * c.P + p) * K + qi) * 2;
-    const double nanv = __builtin_nan("");
     if (live && sub == 0) out_idx[qi] = j;
-    if (live && sub == 0 && j < 0) {
-        out_uv[0] = nanv;
-        out_uv[1] = nanv;
-    }
     int qx = 0, qy = 0;
     if (j >= 0) {
         const int W = c.g.W[l];
@@ -570,51 +657,22 @@ __global__ __launch_bounds__(256) void k_refine_temporal(BatchCtx c) {
         // stage: rows 0..10 the patch (3 dwords via row11), rows 11..25 the window (15 bytes from
         // 5 aligned dwords + alignbyte); row r by sub-lane r % 8
         for (int hl = sub; hl < TS_RT_AROWS + TS_RT_BROWS; hl += 8) {
-            if (hl < TS_RT_AROWS) {
-                uint32_t w3[3];
-                row11(A, W, py - TS_SAD_HALF + hl, px - TS_SAD_HALF, w3);
-                s_a[qslot][hl] = uint4{w3[0], w3[1], w3[2], 0u};
-            } else {
-                const int r = hl - TS_RT_AROWS;
-                const uint8_t* a = B + (size_t)(qy - TS_SAD_HALF - TS_SAD_RANGE + r) * W + (qx - TS_SAD_HALF - TS_SAD_RANGE);
-                const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3u);
-                const uint32_t* q = reinterpret_cast<const uint32_t*>(a - sh);
-                const uint32_t d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3], d4 = q[4];
-                s_b[qslot][r] = uint4{__builtin_amdgcn_alignbyte(d1, d0, sh), __builtin_amdgcn_alignbyte(d2, d1, sh),
-                                      __builtin_amdgcn_alignbyte(d3, d2, sh), __builtin_amdgcn_alignbyte(d4, d3, sh) & 0x00FFFFFFu};
-            }
+            if (hl < TS_RT_AROWS)
+                s_a[qslot][hl] = stage_row11(A, W, py - TS_SAD_HALF + hl, px - TS_SAD_HALF);
+            else
+                s_b[qslot][hl - TS_RT_AROWS] = stage_row15(B, W, qy - TS_SAD_HALF - TS_SAD_RANGE + hl - TS_RT_AROWS,
+                                                           qx - TS_SAD_HALF - TS_SAD_RANGE);
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // staged rows before the reads (own wave)
-    // sub-lane kx < 5 scores the 5 offsets (kx, ky = 0..4) of its column shift: each window row is
-    // realigned once (its 11 bytes from kx on) and serves every ky it meets (patch row dy = r - ky);
-    // the sums are integers, so the costs equal a per-offset loop's
+    // sub-lane kx < 5 scores the 5 offsets (kx, ky = 0..4) of its column shift
     uint32_t key = 0xFFFFFFFFu;   // first minimum of (cost << 5 | offset) over this lane's offsets
     if (j >= 0 && sub < 5) {
-        const int kx = sub, kh = kx >> 2;
-        const uint32_t sh = (uint32_t)(kx & 3);
-        const uint32_t* wb = reinterpret_cast<const uint32_t*>(&s_b[qslot][0]);
-        uint32_t s[5] = {0u, 0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int r = 0; r < TS_RT_BROWS; ++r) {
-            // kx == 4: start one word later with no byte shift (the 4th word is then unused)
-            const uint32_t d0 = wb[4 * r + kh], d1 = wb[4 * r + kh + 1], d2 = wb[4 * r + kh + 2], d3 = wb[4 * r + 3 - kh];
-            const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, sh);
-            const uint32_t w1 = __builtin_amdgcn_alignbyte(d2, d1, sh);
-            const uint32_t w2 = __builtin_amdgcn_alignbyte(d3, d2, sh) & 0x00FFFFFFu;
-#pragma unroll
-            for (int ky = 0; ky < 5; ++ky) {
-                const int dy = r - ky;
-                if (dy < 0 || dy >= TS_RT_AROWS) continue;   // compile-time
-                const uint4 ra = s_a[qslot][dy];
-                s[ky] = __builtin_amdgcn_sad_u8(ra.x, w0, s[ky]);
-                s[ky] = __builtin_amdgcn_sad_u8(ra.y, w1, s[ky]);
-                s[ky] = __builtin_amdgcn_sad_u8(ra.z, w2, s[ky]);
-            }
-        }
+        uint32_t s[5];
+        temporal_sad(s_a[qslot], s_b[qslot], sub, s);
 #pragma unroll
         for (int ky = 0; ky < 5; ++ky) {
-            const int o = ky * 5 + kx;
+            const int o = ky * 5 + sub;
             s_cost[qslot][o] = (int)s[ky];
             key = min(key, (s[ky] << 5) | (uint32_t)o);
         }
@@ -622,23 +680,133 @@ __global__ __launch_bounds__(256) void k_refine_temporal(BatchCtx c) {
 #pragma unroll
     for (int m = 1; m < 8; m <<= 1) key = min(key, (uint32_t)__shfl_xor((int)key, m, 64));
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // costs of the 8 lanes before the reads
-    if (j >= 0 && sub == 0) {
-        const int a = (int)(key & 31u);
-        const int* cq = s_cost[qslot];
-        const int c0 = cq[a];
-        const int cl = cq[max(a - 1, 0)], cr = cq[min(a + 1, 24)];
-        const int cu = cq[max(a - 5, 0)], cd = cq[min(a + 5, 24)];
-        const int ky = a / 5, kx = a % 5;
-        double u = nanv, v = nanv;
-        if (kx > 0 && kx < 4 && ky > 0 && ky < 4) {
-            const double ddx = parabola(cl, c0, cr);
-            const double ddy = parabola(cu, c0, cd);
-            const double sc = (double)(1 << l);
-            u = (((double)(qx + (kx - TS_SAD_RANGE)) + ddx) + 0.5) * sc - 0.5;
-            v = (((double)(qy + (ky - TS_SAD_RANGE)) + ddy) + 0.5) * sc - 0.5;
+    if (live && sub == 0) temporal_store(out_uv, j, l, qx, qy, (int)(key & 31u), s_cost[qslot]);
+}
+
+// Both refinements of a stereo frame in one pass over the left queries (the stereo rig's default:
+// launch_match_refine).  The two kernels above share the query's record, walk the same kind of
+// lookup chain and gather overlapping pixels: the stereo kernel's 11x11 left patch is rows 2..12,
+// bytes 2..12 of the temporal kernel's 15x15 window.  Here a query loads its record and both
+// modes' (qbest, qsecond) in one round and both trains' (tbest, keypoint word) in the next, then
+// stages each image region once, its rows dealt over the 8 sub-lanes with every round's loads in
+// flight together (one instruction stream: any row is 15 bytes from 5 aligned dwords; the t-1
+// patch rows are cut to 11):
+//   rows  0..14  the window at t (temporal match), or its rows 2..12 only (stereo match alone)
+//   rows 15..25  the 11x11 patch at t-1            (temporal match)
+//   rows 26..36  the 15x11 right window            (stereo match)
+// 37 rows in 5 rounds with both matches, where the two kernels gather 22 + 26.  Sub-lanes 0..4 then
+// score the temporal column shifts and the 5 stereo offsets (the lanes of a wave share one
+// instruction stream, so handing the stereo offsets to sub-lanes 5..7 would add their 2 x 11 rows
+// to every wave's time instead of 11).  Outputs are bit for bit the two kernels'.
+#define TS_RP_QPB 32   // queries per block
+#define TS_RP_ROWS (TS_RT_BROWS + TS_RT_AROWS + 11)
+#define TS_RP_ROUNDS ((TS_RP_ROWS + 7) / 8)
+__global__ __launch_bounds__(256) void k_refine_pair(BatchCtx c) {
+    TS_BACK_PRIO;
+    __shared__ uint4 s_rows[TS_RP_QPB][TS_RP_ROWS];
+    __shared__ int s_ct[TS_RP_QPB][25];
+    __shared__ int s_cs[TS_RP_QPB][5];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int K = c.g.K;
+    int z, local;
+    if (!xcd_image_block(blockIdx.x, c.n * c.npair, (K + TS_RP_QPB - 1) / TS_RP_QPB, &z, &local)) return;
+    const int p = c.pair0 + z % c.npair, f = z / c.npair;
+    const int64_t g = c.g0 + f;
+    const int slot = ring_slot(c, g);
+    const int pslot = g > 0 ? ring_slot(c, g - 1) : slot;   // frame 0: nothing matches
+    const int sub = lane & 7;
+    const int qslot = wave * 8 + (lane >> 3);
+    const int pos = local * TS_RP_QPB + qslot;
+    const bool live = pos < K;
+    const size_t mbase = ((size_t)f * c.P + p) * 2 * K;   // stereo; temporal at + K
+    const int qcam = c.cpp * p;
+    const size_t qkb = ((size_t)slot * c.C + qcam) * K;
+    int l = 0, qi = 0, js = -1, jt = -1;
+    uint32_t qxy = 0, tkp = 0, pxy = 0;
+    if (live) {
+        const uint4 rec = c.ys[qkb + pos];
+        qi = (int)rec.z;
+        l = (int)(rec.y & 0xFFu);
+        qxy = rec.x;
+        MatchRef ms, mt;
+        match_query(c, mbase, pos, &ms);
+        match_query(c, mbase + K, pos, &mt);
+        match_train(c, mbase, ((size_t)slot * c.C + qcam + 1) * K, &ms, &tkp);
+        match_train(c, mbase + K, ((size_t)pslot * c.C + qcam) * K, &mt, &pxy);
+        js = match_accept(c, ms, qi, rec.w != 0);
+        jt = match_accept(c, mt, qi, rec.w != 0 && g > 0);
+    }
+    const size_t out = ((size_t)slot * c.P + p) * K + qi;
+    if (live && sub == 0) c.temporal[out] = jt;
+    const int qx = qxy & 0xFFFF, qy = qxy >> 16, xr = tkp & 0xFFFF;
+    {
+        // the level's pitch and offset by selects over the (uniform) table: indexing it by the
+        // lane's level is a load, one more dependent round
+        int W = c.g.W[0], loff = c.g.pyr_off[0];
+#pragma unroll
+        for (int i = 1; i < TS_MAX_LEVELS; ++i)
+            if (l >= i) W = c.g.W[i], loff = c.g.pyr_off[i];
+        const int px = pxy & 0xFFFF, py = pxy >> 16;
+        const uint8_t* cur = c.pyr + ((size_t)slot * c.C + qcam) * c.g.pyr_bytes + loff;
+        const uint8_t* rgt = cur + c.g.pyr_bytes;
+        const uint8_t* prv = c.pyr + ((size_t)pslot * c.C + qcam) * c.g.pyr_bytes + loff;
+        const int nw = jt >= 0 ? TS_RT_BROWS : js >= 0 ? 11 : 0, w0 = jt >= 0 ? 0 : TS_SAD_RANGE;
+        const int np = jt >= 0 ? TS_RT_AROWS : 0;
+        const int total = nw + np + (js >= 0 ? 11 : 0);
+        uint32_t d[TS_RP_ROUNDS][5], sh[TS_RP_ROUNDS];
+#pragma unroll
+        for (int k = 0; k < TS_RP_ROUNDS; ++k) {
+            const int hl = sub + 8 * k;
+            const bool inw = hl < nw, inp = !inw && hl < nw + np;
+            const int r = inw ? hl + w0 : inp ? hl - nw : hl - nw - np;
+            const uint8_t* img = inw ? cur : inp ? prv : rgt;
+            const int y = inw ? qy - TS_SAD_HALF - TS_SAD_RANGE + r : inp ? py - TS_SAD_HALF + r : qy - TS_SAD_HALF + r;
+            const int x0 = inw ? qx - TS_SAD_HALF - TS_SAD_RANGE : inp ? px - TS_SAD_HALF : xr - TS_SAD_HALF - TS_SAD_RANGE;
+            // a lane with no row left loads the level's first bytes (unconditional loads: no
+            // branch, so no wait, between the rounds)
+            const uint8_t* a = hl < total ? img + (size_t)y * W + x0 : cur;
+            sh[k] = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3u);
+            const uint32_t* q = reinterpret_cast<const uint32_t*>(a - sh[k]);
+#pragma unroll
+            for (int i = 0; i < 5; ++i) d[k][i] = q[i];
         }
-        out_uv[0] = u;
-        out_uv[1] = v;
+#pragma unroll
+        for (int k = 0; k < TS_RP_ROUNDS; ++k) {
+            const int hl = sub + 8 * k;
+            const bool inw = hl < nw, inp = !inw && hl < nw + np;
+            uint4 v = align_row15(d[k], sh[k]);
+            if (inp) v.z &= 0x00FFFFFFu, v.w = 0u;
+            const int row = inw ? hl + w0 : inp ? TS_RT_BROWS + hl - nw : TS_RT_BROWS + TS_RT_AROWS + hl - nw - np;
+            if (hl < total) s_rows[qslot][row] = v;
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // staged rows before the reads (own wave)
+    const uint4* rows = s_rows[qslot];
+    uint32_t kt = 0xFFFFFFFFu, ks = 0xFFFFFFFFu;   // first minima of (cost << 5 | offset)
+    if (jt >= 0 && sub < 5) {
+        uint32_t s[5];
+        temporal_sad(rows + TS_RT_BROWS, rows, sub, s);
+#pragma unroll
+        for (int ky = 0; ky < 5; ++ky) {
+            const int o = ky * 5 + sub;
+            s_ct[qslot][o] = (int)s[ky];
+            kt = min(kt, (s[ky] << 5) | (uint32_t)o);
+        }
+    }
+    if (js >= 0 && sub < 5) {
+        const uint32_t s = stereo_sad<TS_SAD_RANGE>(rows + TS_SAD_RANGE, rows + TS_RT_BROWS + TS_RT_AROWS, sub);
+        s_cs[qslot][sub] = (int)s;
+        ks = (s << 5) | (uint32_t)sub;
+    }
+#pragma unroll
+    for (int m = 1; m < 8; m <<= 1) {
+        kt = min(kt, (uint32_t)__shfl_xor((int)kt, m, 64));
+        ks = min(ks, (uint32_t)__shfl_xor((int)ks, m, 64));
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // costs of the 5 lanes before the reads
+    if (live && sub == 0) {
+        temporal_store(c.tuv + (((size_t)f * c.P + p) * K + qi) * 2, jt, l, qx, qy, (int)(kt & 31u), s_ct[qslot]);
+        stereo_store(c, out, js, l, qx, xr, (int)(ks & 31u), s_cs[qslot]);
     }
 }
 
@@ -662,6 +830,11 @@ void launch_match_stereo(const BatchCtx& c, hipStream_t s) {
 
 void launch_match_refine(const BatchCtx& c, hipStream_t s) {
     const int K = c.g.K;
+    // a stereo frame's two refinements in one kernel, unless tslam_params.match_refine asks for the two
+    if (!c.rgbd && c.match_modes == 3 && c.mp.refine_split == 0) {
+        hipLaunchKernelGGL(k_refine_pair, dim3(xcd_grid(c.n * c.npair, (K + TS_RP_QPB - 1) / TS_RP_QPB)), dim3(256), 0, s, c);
+        return;
+    }
     if (c.rgbd)
         launch_rgbd_depth(c, s);
     else

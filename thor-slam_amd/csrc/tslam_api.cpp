@@ -426,9 +426,13 @@ static void build_geometry(tslam_handle* h) {
         g.cand_cap[l] = ((g.band_rows[l] + 1) / 2) * (g.W[l] / 2 + 1);
         g.cand_off[l] = co;
         co += g.nbands[l] * g.cand_cap[l];
-        g.dt_nx[l] = (g.W[l] + TS_DT_W - 1) / TS_DT_W;
+        // describe tiles (origins at multiples of the tile size): the tile columns and rows up to
+        // the last that meets the keypoint band [margin, W - margin) x [margin, H - margin).
+        // 640x400: level 0's rows 384..399 and level 1's 192..199 hold no keypoint, 52 -> 44
+        // blocks per image
+        g.dt_nx[l] = (g.W[l] - p.edge_margin + TS_DT_W - 1) / TS_DT_W;
         g.dt_start[l] = g.dt_total;
-        g.dt_total += g.dt_nx[l] * ((g.H[l] + TS_DT_H - 1) / TS_DT_H);
+        g.dt_total += g.dt_nx[l] * ((g.H[l] - p.edge_margin + TS_DT_H - 1) / TS_DT_H);
         g.qtiles[l] = (g.Kq[l] + 127) / 128;   // k_match: TS_MQ queries per block
         g.qtile_start[l] = qs;
         qs += g.qtiles[l];
@@ -749,6 +753,7 @@ static BatchCtx make_ctx(tslam_handle* h) {
     c.mp.row_tol = h->prm.stereo_row_tol;
     c.mp.max_disp = h->prm.max_disparity;
     c.mp.window = h->prm.temporal_window;
+    c.mp.refine_split = h->prm.match_refine;
     c.pp.n_hyp = h->prm.ransac_hypotheses;
     c.pp.iters = h->prm.refine_iters;
     c.pp.min_inliers = h->prm.min_inliers;
@@ -1019,6 +1024,7 @@ int tslam_create(const tslam_stereo_desc* pairs, const tslam_params* params, int
     if (p.ransac_mode < 0 || p.ransac_mode > 2) return fail(TSLAM_EINVAL, "ransac_mode must be 0, 1 or 2");
     if (p.refine_block != 0 && p.refine_block != 128 && p.refine_block != 256)
         return fail(TSLAM_EINVAL, "refine_block must be 0, 128 or 256");
+    if (p.match_refine != 0 && p.match_refine != 1) return fail(TSLAM_EINVAL, "match_refine must be 0 or 1");
     const int W = pairs[0].width, H = pairs[0].height;
     if (W < 64 || H < 64 || W > 2047 || H > 2047) return fail(TSLAM_EINVAL, "image size must be within [64, 2047]");
     for (int i = 1; i < p.n_pairs; ++i)

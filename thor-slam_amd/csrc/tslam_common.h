@@ -83,6 +83,7 @@ struct PairCalib {
 
 struct MatchParams {
     int max_hamming, ratio_pct, row_tol, max_disp, window;
+    int refine_split;   // stereo + temporal refinement: 0 one fused kernel (k_refine_pair), 1 the two kernels
 };
 
 struct PoseParams {

@@ -1,9 +1,13 @@
 """Time single kernels back to back on resident data (profiling aid, not the bench).
 
     python tools/kernel_probe.py [--batch 256] [--kernels rectify_pyramid,detect,detect,detect]
+    python tools/kernel_probe.py --batch 2048 --kernels match_refine --reps 5 --match-refine split,auto
 
 Runs one full batch first (so every buffer holds real data), then launches the listed kernels in
 order inside one batch and prints each launch's duration from HIP events on the launch stream.
+--match-refine takes one variant of the stereo + temporal refinement (auto: the fused kernel,
+split: the two kernels) or several, comma separated: one handle each on the same frames, every
+listed kernel timed on each handle in turn, --reps times over, so the variants alternate.
 Also times a device-to-device copy of the batch's pyramid slice as a bandwidth reference.
 """
 
@@ -28,6 +32,9 @@ def main() -> None:
     ap.add_argument("--ransac-counters", action="store_true",
                     help="print the per-block counters an instrumented k_ransac build leaves in qbest")
     ap.add_argument("--splits", type=int, default=0, help="RANSAC splits per frame (0: the library's choice)")
+    ap.add_argument("--match-refine", default="auto",
+                    help="tslam_params.match_refine: auto (fused) or split, or both comma separated (alternating)")
+    ap.add_argument("--reps", type=int, default=1, help="times the kernel list is run")
     args = ap.parse_args()
     import torch
 
@@ -49,23 +56,31 @@ def main() -> None:
         uniq = src.render_stereo_sequence(16)
     frames = uniq[triangle_indices(2 * B, len(uniq))]
     dev = torch.from_numpy(frames).cuda()
-    h = Handle([rect], HipSlamConfig(n_features=args.features), max_batch=B, ransac_splits=args.splits)
+    variants = args.match_refine.split(",")
+    hs = [Handle([rect], HipSlamConfig(n_features=args.features), max_batch=B, ransac_splits=args.splits, match_refine=v)
+          for v in variants]
+    h = hs[0]
     stream = torch.cuda.current_stream()
     s = stream.cuda_stream
-    h.submit(dev[:B].data_ptr(), B, s)
-    h.submit(dev[B:].data_ptr(), B, s)
+    for hv in hs:
+        hv.submit(dev[:B].data_ptr(), B, s)
+        hv.submit(dev[B:].data_ptr(), B, s)
     torch.cuda.synchronize()
     import numpy as np
 
     print("te per camera x level:", h.frame_block("det_thr", 0, np.uint32).reshape(2, -1).tolist())
-    h.begin_batch(dev[:B].data_ptr(), B)
-    for name in args.kernels.split(","):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        h.run_kernel(name, s)
-        e1.record(stream)
-        torch.cuda.synchronize()
-        print(f"{name:16s} {1000 * e0.elapsed_time(e1):9.1f} us")
+    for hv in hs:
+        hv.begin_batch(dev[:B].data_ptr(), B)
+    for _ in range(args.reps):
+        for name in args.kernels.split(","):
+            for hv, v in zip(hs, variants):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                hv.run_kernel(name, s)
+                e1.record(stream)
+                torch.cuda.synchronize()
+                tag = f" [match_refine={v}]" if len(hs) > 1 else ""
+                print(f"{name:16s} {1000 * e0.elapsed_time(e1):9.1f} us{tag}")
     st = np.stack([h.frame_block("stats", i, np.int32)[:5] for i in range(0, B, max(1, B // 64))])
     ok = st[:, 0] == 0
     print("pose stats over %d sampled frames: tracked %d, correspondences n mean %.0f min %d max %d, "
@@ -80,7 +95,8 @@ def main() -> None:
         print("  max " + " ".join("%s %d" % (k, v) for k, v in zip(names, cnt.max(0))))
         top = np.argsort(-cnt[:, 4])[:5]
         print("  slowest blocks (superchunks):", [(int(i), cnt[i].tolist()) for i in top])
-    h.end_batch()
+    for hv in hs:
+        hv.end_batch()
     # bandwidth reference: copy the pyramid slice of B frames (read + write)
     import ctypes
 
@@ -97,7 +113,8 @@ def main() -> None:
             torch.cuda.synchronize()
             us = 1000 * e0.elapsed_time(e1)
             print(f"copy {nbytes / 1e6:.0f} MB  {us:9.1f} us  {2 * nbytes / us / 1e3:.0f} GB/s")
-    h.close()
+    for hv in hs:
+        hv.close()
 
 
 if __name__ == "__main__":
