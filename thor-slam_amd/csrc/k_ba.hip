@@ -1660,7 +1660,7 @@ void launch_ba_solve(const BatchCtx& c, const BaArgs& a, hipStream_t s, BaTiming
 }
 
 // ---------------------------------------------------------------------------------------------
-// the keyframe chain by record (graph replays, tslam_api.cpp ba_chain)
+// the keyframe chain by record (graph replays, tslam_api_ba.cpp ba_chain_graph)
 // ---------------------------------------------------------------------------------------------
 struct BaRecWords {
     uint64_t w[(sizeof(BaRec) + 7) / 8];

@@ -1,0 +1,451 @@
+// tslam_api_dense.cpp — the dense map on the host side: TSDF integration, dense stereo depth, and
+// the outputs of the volume (marching-cubes mesh, ESDF, ESDF slice).
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "tslam_handle.h"
+
+static size_t tsdf_voxels(const tslam_handle* h) { return (size_t)h->tsdf.nx * h->tsdf.ny * h->tsdf.nz; }
+
+// the synchronous reads and writes below: every stream's work on the map is done
+static int dense_quiesce(tslam_handle* h) {
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceSynchronize());
+    return TSLAM_OK;
+}
+
+// tslam_reset: the volume belongs to the session (the stereo depth slots do not: they stay)
+int dense_reset(tslam_handle* h) {
+    if (h->tsdf_on) {
+        const size_t nv = tsdf_voxels(h);
+        HIPCHK(hipMemset(h->tsdf.tsdf, 0, sizeof(float) * nv));
+        HIPCHK(hipMemset(h->tsdf.weight, 0, sizeof(float) * nv));
+        if (h->tsdf.col) {
+            HIPCHK(hipMemset(h->tsdf.col, 0, sizeof(float) * 3 * nv));
+            HIPCHK(hipMemset(h->tsdf.col_w, 0, sizeof(float) * nv));
+        }
+    }
+    return TSLAM_OK;
+}
+
+extern "C" {
+
+// -- RGB-D dense mapping: TSDF integration -------------------------------------------------------
+int tslam_tsdf_init(tslam_handle* h, const double* origin, const int32_t* dims, double voxel_size, double trunc_vox,
+                    double max_dist, double max_weight) {
+    if (!h || !origin || !dims) return fail(TSLAM_EINVAL, "bad argument");
+    BA_FLUSH(h);
+    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1 || (int64_t)dims[0] * dims[1] * dims[2] > ((int64_t)1 << 31))
+        return fail(TSLAM_EINVAL, "dims must be >= 1 with at most 2^31 voxels");
+    if (!(voxel_size > 0.0) || !(trunc_vox > 0.0) || !(max_dist > 0.0) || !(max_weight >= 1.0))
+        return fail(TSLAM_EINVAL, "voxel_size, trunc_vox, max_dist must be > 0 and max_weight >= 1");
+    if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
+    const size_t nv = (size_t)dims[0] * dims[1] * dims[2];
+    TsdfArgs& a = h->tsdf;
+    int rc = dev_grow(h, (void**)&a.tsdf, sizeof(float) * nv);
+    if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&a.weight, sizeof(float) * nv);
+    if (rc == TSLAM_OK && h->tsdf_color) {
+        rc = dev_grow(h, (void**)&a.col, sizeof(float) * 3 * nv);
+        if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&a.col_w, sizeof(float) * nv);
+    }
+    if (rc == TSLAM_OK && !h->d_tsdf_poses) rc = dev_alloc(h, (void**)&h->d_tsdf_poses, sizeof(double) * TSDF_MAX_FRAMES * TSDF_POSE);
+    if (rc == TSLAM_OK && !h->d_tsdf_wTc) rc = dev_alloc(h, (void**)&h->d_tsdf_wTc, sizeof(double) * TSDF_MAX_FRAMES * 16);
+    if (rc != TSLAM_OK) return rc;
+    a.nx = dims[0];
+    a.ny = dims[1];
+    a.nz = dims[2];
+    a.ox = origin[0];
+    a.oy = origin[1];
+    a.oz = origin[2];
+    a.s = voxel_size;
+    a.trunc = trunc_vox * voxel_size;
+    a.max_dist = max_dist;
+    a.max_weight = max_weight;
+    h->tsdf_on = true;
+    h->esdf_valid = false;   // outputs of the previous volume are gone
+    h->mesh_n = 0;
+    return TSLAM_OK;
+}
+
+static int tsdf_integrate(tslam_handle* h, int pair, const void* color, const void* depth, int64_t stride_bytes,
+                          int n_frames, int64_t first_frame, const double* world_T_cam, void* stream, bool rect = false) {
+    if (!h || pair < 0 || pair >= h->P) return fail(TSLAM_EINVAL, "bad handle or pair");
+    BA_FLUSH(h);
+    if (!h->tsdf_on) return fail(TSLAM_ESTATE, "no TSDF volume (tslam_tsdf_init)");
+    if (!depth || n_frames < 0 || (n_frames > 1 && stride_bytes < 2LL * h->W * h->H)) return fail(TSLAM_EINVAL, "bad depth / stride");
+    if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_tsdf_integrate inside a batch");
+    int f0 = 0;
+    if (!world_T_cam) {   // device poses: frames of the last batch
+        f0 = (int)(first_frame - h->cur_g0);
+        if (first_frame < h->cur_g0 || f0 + n_frames > h->cur_n)
+            return fail(TSLAM_EINVAL, "device poses: frames must belong to the last batch");
+    }
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = stream ? (hipStream_t)stream : h->last_stream;
+    const BatchCtx c = make_ctx(h);
+    const int cam = c.cpp * pair;
+    TsdfArgs a = h->tsdf;
+    a.W = h->W;
+    a.H = h->H;
+    a.fx = h->calib[pair].fx;
+    a.fy = h->calib[pair].fy;
+    a.cx = h->calib[pair].cx;
+    a.cy = h->calib[pair].cy;
+    // rect: the depth lives in the pair's rectified camera already (tslam_stereo_depth)
+    a.map = (!rect && ((h->map_mask >> cam) & 1u)) ? h->d_maps + (size_t)cam * h->W * h->H * 2 : nullptr;
+    a.stride = stride_bytes;
+    if (!color) a.col = a.col_w = nullptr;   // the colour layer keeps its state without colour input
+    for (int b0 = 0; b0 < n_frames; b0 += TSDF_MAX_FRAMES) {
+        a.n = std::min(TSDF_MAX_FRAMES, n_frames - b0);
+        a.depth = static_cast<const uint8_t*>(depth) + (size_t)b0 * stride_bytes;
+        a.color = color ? static_cast<const uint8_t*>(color) + (size_t)b0 * stride_bytes : nullptr;
+        const double* wtc = nullptr;
+        if (world_T_cam) {
+            HIPCHK(hipMemcpyAsync(h->d_tsdf_wTc, world_T_cam + (size_t)16 * b0, sizeof(double) * 16 * a.n,
+                                  hipMemcpyHostToDevice, s));
+            wtc = h->d_tsdf_wTc;
+        }
+        launch_tsdf(c, pair, f0 + b0, wtc, a, h->d_tsdf_poses, s);
+        HIPCHK(hipGetLastError());
+        if (world_T_cam) HIPCHK(hipStreamSynchronize(s));   // the staged host poses are reused
+    }
+    return TSLAM_OK;
+}
+
+int tslam_tsdf_integrate(tslam_handle* h, int pair, const void* depth, int64_t stride_bytes, int n_frames,
+                         int64_t first_frame, const double* world_T_cam, void* stream) {
+    return tsdf_integrate(h, pair, nullptr, depth, stride_bytes, n_frames, first_frame, world_T_cam, stream);
+}
+
+int tslam_tsdf_integrate_rgbd(tslam_handle* h, int pair, const void* color, const void* depth, int64_t stride_bytes,
+                              int n_frames, int64_t first_frame, const double* world_T_cam, void* stream) {
+    if (!color) return fail(TSLAM_EINVAL, "null colour images");
+    if (h && !h->tsdf_color) return fail(TSLAM_ESTATE, "no colour layer (tslam_tsdf_color before tslam_tsdf_init)");
+    return tsdf_integrate(h, pair, color, depth, stride_bytes, n_frames, first_frame, world_T_cam, stream);
+}
+
+int tslam_tsdf_color(tslam_handle* h, int enable) {
+    if (!h) return fail(TSLAM_EINVAL, "null handle");
+    if (h->tsdf_on && (enable != 0) != h->tsdf_color) return fail(TSLAM_ESTATE, "tslam_tsdf_color before tslam_tsdf_init");
+    h->tsdf_color = enable != 0;
+    return TSLAM_OK;
+}
+
+int tslam_tsdf_integrate_rect(tslam_handle* h, int pair, const void* depth, int64_t stride_bytes, int n_frames,
+                              int64_t first_frame, const double* world_T_cam, void* stream) {
+    return tsdf_integrate(h, pair, nullptr, depth, stride_bytes, n_frames, first_frame, world_T_cam, stream, true);
+}
+
+// -- dense stereo depth ------------------------------------------------------------------------------
+int tslam_stereo_depth_init(tslam_handle* h, const tslam_stereo_depth_params* params, int max_frames) {
+    if (!h || !params) return fail(TSLAM_EINVAL, "bad argument");
+    if (h->prm.rgbd) return fail(TSLAM_ESTATE, "dense stereo depth needs a stereo handle (this one is RGB-D)");
+    if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_stereo_depth_init inside a batch");
+    tslam_stereo_depth_params p = *params;
+    if (p.n_disp == 0) p.n_disp = std::min(256, std::max(4, (int)h->prm.max_disparity));
+    if (p.n_disp < 4 || p.n_disp > 256) return fail(TSLAM_EINVAL, "n_disp must be 4..256 (0 = max_disparity)");
+    if (p.uniqueness < 0 || p.uniqueness > 99) return fail(TSLAM_EINVAL, "uniqueness must be 0..99");
+    if (p.lr_tol < 0 || p.reserved != 0) return fail(TSLAM_EINVAL, "lr_tol must be >= 0 and reserved 0");
+    if (max_frames < 1 || max_frames > 65535) return fail(TSLAM_EINVAL, "max_frames must be 1..65535");
+    BA_FLUSH(h);
+    if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
+    const size_t px = (size_t)max_frames * h->W * h->H;
+    int rc = dev_grow(h, (void**)&h->d_sd_depth, 2 * px);
+    if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&h->d_sd_disp, 2 * px);
+    if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&h->d_sd_win, 2 * px);
+    if (rc != TSLAM_OK) {
+        h->sd_on = false;
+        return rc;
+    }
+    h->sd_prm = p;
+    h->sd_frames = max_frames;
+    h->sd_w = h->W;
+    h->sd_h = h->H;
+    h->sd_on = true;
+    return TSLAM_OK;
+}
+
+static int stereo_depth_run(tslam_handle* h, StereoDepthArgs a, void* stream) {
+    a.n_disp = h->sd_prm.n_disp;
+    a.uniqueness = h->sd_prm.uniqueness;
+    a.lr_tol = h->sd_prm.lr_tol;
+    a.depth = h->d_sd_depth;
+    a.disp32 = h->d_sd_disp;
+    a.win_left = h->d_sd_win;
+    a.win_right = h->d_sd_win + (size_t)h->sd_frames * h->W * h->H;
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = stream ? (hipStream_t)stream : h->last_stream;
+    HIPCHK(launch_stereo_depth(a, s));
+    h->sd_w = a.W;
+    h->sd_h = a.H;
+    return TSLAM_OK;
+}
+
+int tslam_stereo_depth(tslam_handle* h, int pair, int64_t first_frame, int n_frames, void* stream) {
+    if (!h || pair < 0 || pair >= h->P) return fail(TSLAM_EINVAL, "bad handle or pair");
+    if (!h->sd_on) return fail(TSLAM_ESTATE, "no stereo depth buffers (tslam_stereo_depth_init)");
+    if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_stereo_depth inside a batch");
+    if (n_frames < 0 || n_frames > h->sd_frames) return fail(TSLAM_EINVAL, "n_frames must be 0..max_frames");
+    if (first_frame < h->cur_g0 || first_frame - h->cur_g0 + n_frames > h->cur_n)
+        return fail(TSLAM_EINVAL, "frames must belong to the last batch");
+    BA_FLUSH(h);
+    const uint8_t* pyr = static_cast<const uint8_t*>(h->buf[TSLAM_BUF_PYRAMID].ptr);
+    StereoDepthArgs a{};
+    a.stride = (int64_t)h->C * h->g.pyr_bytes;
+    a.left = pyr + (size_t)(2 * pair) * h->g.pyr_bytes + h->g.pyr_off[0];
+    a.right = a.left + h->g.pyr_bytes;
+    a.ring = h->R;
+    a.first = first_frame;
+    a.W = h->W;
+    a.H = h->H;
+    a.n = n_frames;
+    a.fxb = h->calib[pair].fxb;
+    return stereo_depth_run(h, a, stream);
+}
+
+int tslam_stereo_depth_images(tslam_handle* h, const uint8_t* left, const uint8_t* right, int64_t frame_stride, int width,
+                              int height, double fxb, int n_frames, void* stream) {
+    if (!h || !left || !right) return fail(TSLAM_EINVAL, "bad argument");
+    if (!h->sd_on) return fail(TSLAM_ESTATE, "no stereo depth buffers (tslam_stereo_depth_init)");
+    if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_stereo_depth_images inside a batch");
+    if (n_frames < 0 || n_frames > h->sd_frames) return fail(TSLAM_EINVAL, "n_frames must be 0..max_frames");
+    if (width < 16 || height < 16 || width > h->W || height > h->H)
+        return fail(TSLAM_EINVAL, "width / height must be 16 .. the handle's size");
+    if (n_frames > 1 && frame_stride < (int64_t)width * height) return fail(TSLAM_EINVAL, "frame_stride below one image");
+    if (!(fxb > 0.0)) return fail(TSLAM_EINVAL, "fxb must be > 0");
+    BA_FLUSH(h);
+    StereoDepthArgs a{};
+    a.left = left;
+    a.right = right;
+    a.stride = frame_stride;
+    a.W = width;
+    a.H = height;
+    a.n = n_frames;
+    a.fxb = fxb;
+    return stereo_depth_run(h, a, stream);
+}
+
+int tslam_stereo_depth_buffers(tslam_handle* h, void** depth, void** disp32, int64_t* frame_bytes) {
+    if (!h) return fail(TSLAM_EINVAL, "null handle");
+    if (!h->sd_on) return fail(TSLAM_ESTATE, "no stereo depth buffers (tslam_stereo_depth_init)");
+    if (depth) *depth = h->d_sd_depth;
+    if (disp32) *disp32 = h->d_sd_disp;
+    if (frame_bytes) *frame_bytes = 2LL * h->W * h->H;
+    return TSLAM_OK;
+}
+
+int tslam_stereo_depth_read(tslam_handle* h, int slot, uint16_t* depth, uint16_t* disp32) {
+    if (!h) return fail(TSLAM_EINVAL, "null handle");
+    if (!h->sd_on) return fail(TSLAM_ESTATE, "no stereo depth buffers (tslam_stereo_depth_init)");
+    if (slot < 0 || slot >= h->sd_frames) return fail(TSLAM_EINVAL, "slot out of range");
+    BA_FLUSH(h);
+    if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
+    const size_t px = (size_t)h->sd_w * h->sd_h;
+    if (depth) HIPCHK(hipMemcpy(depth, h->d_sd_depth + px * slot, 2 * px, hipMemcpyDeviceToHost));
+    if (disp32) HIPCHK(hipMemcpy(disp32, h->d_sd_disp + px * slot, 2 * px, hipMemcpyDeviceToHost));
+    return TSLAM_OK;
+}
+
+int tslam_tsdf_read(tslam_handle* h, float* tsdf, float* weight) {
+    if (!h || !h->tsdf_on) return fail(TSLAM_ESTATE, "no TSDF volume (tslam_tsdf_init)");
+    BA_FLUSH(h);
+    if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
+    const size_t nv = tsdf_voxels(h);
+    if (tsdf) HIPCHK(hipMemcpy(tsdf, h->tsdf.tsdf, sizeof(float) * nv, hipMemcpyDeviceToHost));
+    if (weight) HIPCHK(hipMemcpy(weight, h->tsdf.weight, sizeof(float) * nv, hipMemcpyDeviceToHost));
+    return TSLAM_OK;
+}
+
+int tslam_tsdf_read_color(tslam_handle* h, float* rgb, float* weight) {
+    if (!h || !h->tsdf_on || !h->tsdf_color) return fail(TSLAM_ESTATE, "no colour layer");
+    if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
+    const size_t nv = tsdf_voxels(h);
+    if (rgb) HIPCHK(hipMemcpy(rgb, h->tsdf.col, sizeof(float) * 3 * nv, hipMemcpyDeviceToHost));
+    if (weight) HIPCHK(hipMemcpy(weight, h->tsdf.col_w, sizeof(float) * nv, hipMemcpyDeviceToHost));
+    return TSLAM_OK;
+}
+
+int tslam_tsdf_write_color(tslam_handle* h, const float* rgb, const float* weight) {
+    if (!h || !h->tsdf_on || !h->tsdf_color) return fail(TSLAM_ESTATE, "no colour layer");
+    if (!rgb || !weight) return fail(TSLAM_EINVAL, "null colour volume");
+    if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
+    const size_t nv = tsdf_voxels(h);
+    HIPCHK(hipMemcpy(h->tsdf.col, rgb, sizeof(float) * 3 * nv, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->tsdf.col_w, weight, sizeof(float) * nv, hipMemcpyHostToDevice));
+    return TSLAM_OK;
+}
+
+int tslam_tsdf_write(tslam_handle* h, const float* tsdf, const float* weight) {
+    if (!h || !h->tsdf_on) return fail(TSLAM_ESTATE, "no TSDF volume (tslam_tsdf_init)");
+    BA_FLUSH(h);
+    if (!tsdf || !weight) return fail(TSLAM_EINVAL, "null volume");
+    if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
+    const size_t nv = tsdf_voxels(h);
+    HIPCHK(hipMemcpy(h->tsdf.tsdf, tsdf, sizeof(float) * nv, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->tsdf.weight, weight, sizeof(float) * nv, hipMemcpyHostToDevice));
+    h->esdf_valid = false;
+    return TSLAM_OK;
+}
+
+// -- dense-map outputs: marching-cubes mesh, ESDF, 2-D ESDF slice (k_dense.hip) ------------------
+static DenseArgs dense_args(const tslam_handle* h, double min_weight) {
+    const TsdfArgs& t = h->tsdf;
+    DenseArgs a{};
+    a.tsdf = t.tsdf;
+    a.weight = t.weight;
+    a.nx = t.nx;
+    a.ny = t.ny;
+    a.nz = t.nz;
+    a.n_cubes = (t.nx > 1 && t.ny > 1 && t.nz > 1) ? (uint32_t)((int64_t)(t.nx - 1) * (t.ny - 1) * (t.nz - 1)) : 0u;
+    a.n_voxels = (int64_t)t.nx * t.ny * t.nz;
+    a.ox = t.ox;
+    a.oy = t.oy;
+    a.oz = t.oz;
+    a.s = t.s;
+    a.sf = (float)t.s;
+    a.min_weight = (float)min_weight;
+    a.color = h->tsdf_color ? t.col : nullptr;
+    return a;
+}
+
+int tslam_mesh_extract(tslam_handle* h, double min_weight, int64_t* n_tris, void* stream) {
+    if (!h || !h->tsdf_on) return fail(TSLAM_ESTATE, "no TSDF volume (tslam_tsdf_init)");
+    BA_FLUSH(h);
+    if (!(min_weight >= 0.0)) return fail(TSLAM_EINVAL, "min_weight must be >= 0");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = stream ? (hipStream_t)stream : h->last_stream;
+    const DenseArgs a = dense_args(h, min_weight);
+    h->mesh_n = 0;
+    if (a.n_cubes == 0) {
+        if (n_tris) *n_tris = 0;
+        return TSLAM_OK;
+    }
+    const size_t nb = (a.n_cubes + 255) / 256;
+    size_t cap = h->mesh_cubes_cap;
+    if (cap < a.n_cubes) {   // the three scratch arrays follow the cube count
+        int rc = dev_grow(h, (void**)&h->d_mesh_cfg, a.n_cubes);
+        if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&h->d_mesh_bsum, sizeof(uint32_t) * nb);
+        if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&h->d_mesh_boff, sizeof(uint64_t) * (nb + 1));
+        if (rc != TSLAM_OK) return rc;
+        h->mesh_cubes_cap = a.n_cubes;
+    }
+    launch_mesh_count(a, h->d_mesh_cfg, h->d_mesh_bsum, h->d_mesh_boff, h->d_mesh_boff + nb, s);
+    HIPCHK(hipGetLastError());
+    uint64_t total = 0;   // the buffer is sized to the count: one small read back
+    HIPCHK(hipMemcpyAsync(&total, h->d_mesh_boff + nb, sizeof(total), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if ((int64_t)total > h->mesh_tris_cap || (a.color && !h->d_mesh_cols)) {
+        const int64_t want = std::max((int64_t)total + (int64_t)total / 4 + 1024, h->mesh_tris_cap);
+        int rc = dev_grow(h, (void**)&h->d_mesh_tris, sizeof(float) * 9 * (size_t)want);
+        if (rc == TSLAM_OK && a.color) rc = dev_grow(h, (void**)&h->d_mesh_cols, sizeof(float) * 9 * (size_t)want);
+        if (rc != TSLAM_OK) return rc;
+        h->mesh_tris_cap = want;
+    }
+    launch_mesh_emit(a, h->d_mesh_cfg, h->d_mesh_boff, h->d_mesh_tris, h->d_mesh_cols, h->mesh_tris_cap, s);
+    HIPCHK(hipGetLastError());
+    h->mesh_n = (int64_t)total;
+    if (n_tris) *n_tris = (int64_t)total;
+    return TSLAM_OK;
+}
+
+int tslam_mesh_read_colors(tslam_handle* h, float* colors, int64_t max_tris) {
+    if (!h || !h->tsdf_on || !h->tsdf_color || !h->d_mesh_cols) return fail(TSLAM_ESTATE, "no colour layer mesh");
+    if (max_tris < 0 || (max_tris > 0 && !colors)) return fail(TSLAM_EINVAL, "bad buffer");
+    if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
+    const int64_t n = std::min(max_tris, h->mesh_n);
+    if (n > 0) HIPCHK(hipMemcpy(colors, h->d_mesh_cols, sizeof(float) * 9 * (size_t)n, hipMemcpyDeviceToHost));
+    return TSLAM_OK;
+}
+
+int tslam_mesh_read(tslam_handle* h, float* tris, int64_t max_tris) {
+    if (!h || !h->tsdf_on) return fail(TSLAM_ESTATE, "no TSDF volume (tslam_tsdf_init)");
+    if (max_tris < 0 || (max_tris > 0 && !tris)) return fail(TSLAM_EINVAL, "bad buffer");
+    if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
+    const int64_t n = std::min(max_tris, h->mesh_n);
+    if (n > 0) HIPCHK(hipMemcpy(tris, h->d_mesh_tris, sizeof(float) * 9 * (size_t)n, hipMemcpyDeviceToHost));
+    return TSLAM_OK;
+}
+
+// f32 distance of every squared voxel distance 0..R^2 (sqrt in f32, times s in f32, IEEE on the host)
+static int dist_table(tslam_handle* h, int R, double s) {
+    if (h->dist_tab_R == R && h->dist_tab_s == s && h->d_dist_tab) return TSLAM_OK;
+    const size_t n = (size_t)R * R + 1;
+    std::vector<float> tab(n);
+    const float sf = (float)s;
+    for (size_t d = 0; d < n; ++d) tab[d] = std::sqrt((float)d) * sf;
+    const int rc = dev_grow(h, (void**)&h->d_dist_tab, sizeof(float) * n);
+    if (rc != TSLAM_OK) return rc;
+    HIPCHK(hipMemcpy(h->d_dist_tab, tab.data(), sizeof(float) * n, hipMemcpyHostToDevice));
+    h->dist_tab_R = R;
+    h->dist_tab_s = s;
+    return TSLAM_OK;
+}
+
+static int esdf_setup(tslam_handle* h, double max_dist, double site_vox, double min_weight, size_t cells, DenseArgs* a,
+                      int* R) {
+    if (!h || !h->tsdf_on) return fail(TSLAM_ESTATE, "no TSDF volume (tslam_tsdf_init)");
+    if (!(max_dist > 0.0) || !(site_vox >= 0.0) || !(min_weight >= 0.0))
+        return fail(TSLAM_EINVAL, "max_dist must be > 0, site_vox and min_weight >= 0");
+    const double r = std::floor(max_dist / h->tsdf.s + 1e-9);
+    if (r < 0.0 || r > 2048.0) return fail(TSLAM_EINVAL, "max_dist / voxel_size must be at most 2048 voxels");
+    HIPCHK(hipSetDevice(h->device));
+    *R = (int)r;
+    *a = dense_args(h, min_weight);
+    a->site_dist = (float)(site_vox * h->tsdf.s);
+    a->max_dist = (float)max_dist;
+    a->cap = *R * *R + 1;
+    int rc = dist_table(h, *R, h->tsdf.s);
+    if (rc == TSLAM_OK && h->edt_cap < cells) {
+        rc = dev_grow(h, (void**)&h->d_edt[0], sizeof(int32_t) * cells);
+        if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&h->d_edt[1], sizeof(int32_t) * cells);
+        h->edt_cap = rc == TSLAM_OK ? cells : 0;
+    }
+    return rc;
+}
+
+int tslam_esdf_compute(tslam_handle* h, double max_dist, double site_vox, double min_weight, void* stream) {
+    DenseArgs a;
+    int R = 0;
+    const size_t nv = h && h->tsdf_on ? tsdf_voxels(h) : 0;
+    int rc = esdf_setup(h, max_dist, site_vox, min_weight, nv, &a, &R);
+    if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&h->d_esdf, sizeof(float) * nv, &h->esdf_cap);
+    if (rc != TSLAM_OK) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : h->last_stream;
+    launch_esdf(a, R, h->d_dist_tab, h->d_edt[0], h->d_edt[1], h->d_esdf, s);
+    HIPCHK(hipGetLastError());
+    h->esdf_valid = true;
+    return TSLAM_OK;
+}
+
+int tslam_esdf_read(tslam_handle* h, float* esdf) {
+    if (!h || !h->tsdf_on || !h->esdf_valid) return fail(TSLAM_ESTATE, "no ESDF (tslam_esdf_compute)");
+    if (!esdf) return fail(TSLAM_EINVAL, "null buffer");
+    if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
+    const size_t nv = tsdf_voxels(h);
+    HIPCHK(hipMemcpy(esdf, h->d_esdf, sizeof(float) * nv, hipMemcpyDeviceToHost));
+    return TSLAM_OK;
+}
+
+int tslam_esdf_slice(tslam_handle* h, int y0, int y1, double max_dist, double site_vox, double min_weight, float* out) {
+    if (!h || !h->tsdf_on) return fail(TSLAM_ESTATE, "no TSDF volume (tslam_tsdf_init)");
+    if (!out || y0 < 0 || y1 <= y0 || y1 > h->tsdf.ny) return fail(TSLAM_EINVAL, "need 0 <= y0 < y1 <= ny and a buffer");
+    DenseArgs a;
+    int R = 0;
+    const size_t nc = (size_t)h->tsdf.nx * h->tsdf.nz;
+    int rc = esdf_setup(h, max_dist, site_vox, min_weight, nc, &a, &R);
+    if (rc == TSLAM_OK && h->slice_cap < nc) {
+        rc = dev_grow(h, (void**)&h->d_slice_obs, nc);
+        if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&h->d_slice, sizeof(float) * nc);
+        h->slice_cap = rc == TSLAM_OK ? nc : 0;
+    }
+    if (rc != TSLAM_OK) return rc;
+    hipStream_t s = h->last_stream;
+    launch_esdf_slice(a, y0, y1, R, h->d_dist_tab, h->d_edt[0], h->d_edt[1], h->d_slice_obs, h->d_slice, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpy(out, h->d_slice, sizeof(float) * nc, hipMemcpyDeviceToHost));
+    return TSLAM_OK;
+}
+
+}  // extern "C"

@@ -148,7 +148,7 @@ __device__ __forceinline__ BaPair ba_pair(const BatchCtx& c, const BaArgs& a, in
     q.X = s.X + p * WK * 3;
     q.kf_desc = s.kf_desc + p * WK * 8;
     q.gid = s.gid + p * WK;
-    // per-pair scratch (strides: ba_scratch_sizes in tslam_api.cpp)
+    // per-pair scratch (sizes: alloc_ba in tslam_api_ba.cpp)
     q.remap = s.remap + p * K; q.cnt = s.cnt + p * WK; q.lm_id = s.lm_id + p * WK;
     q.keep = s.keep + p * WK;
     q.lmask = s.lmask + p * (WK / 32 + 64); q.lpre = s.lpre + p * (WK / 32 + 64);

@@ -1,0 +1,328 @@
+// tslam_handle.h — the handle behind the C-ABI and what the host files of the library share to
+// work on it.  Host only: no .hip file includes it.
+//
+// The fields of tslam_handle are ordered by the file that owns them ("host sources"):
+// a field is written by its owner and by tslam_create; other files go through the helpers
+// declared at the end.  Every helper is TSLAM_INTERNAL: none reaches the dynamic symbol table.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <array>
+#include <condition_variable>
+#include <deque>
+#include <functional>
+#include <map>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/tslam.h"
+#include "tslam_ba.h"
+#include "tslam_common.h"
+#include "tslam_internal.h"
+
+struct Buffer {
+    void* ptr = nullptr;
+    int64_t bytes = 0;
+    int64_t per_frame = 0;
+};
+
+struct tslam_handle {
+    // ---- tslam_api.cpp: geometry, workspace, the current batch, rig, motion prior, host boundary ----
+    int device = 0;
+    tslam_params prm{};
+    int W = 0, H = 0, P = 0, C = 0, B = 0, R = 0;
+    LevelGeom g{};
+    PairCalib calib[8]{};
+    uint32_t map_mask = 0;
+    int32_t* d_maps = nullptr;
+    uint32_t* d_brief = nullptr;
+    int64_t* d_wedges = nullptr;
+    uint8_t* d_gray = nullptr;   // RGB-D: converted colour images [B][P][H][W]
+    Buffer buf[TSLAM_BUF_COUNT];
+    uint32_t* d_cand = nullptr;
+    uint32_t* d_ccount = nullptr;
+    uint32_t* d_det_thr_acc = nullptr;   // [C][L] running minimum of the next te
+    uint32_t* d_hist = nullptr;
+    double* d_state = nullptr;
+    double* d_ransac = nullptr;
+    double* d_hyp = nullptr;
+    int64_t frames_done = 0;
+    // current batch
+    const uint8_t* cur_images = nullptr;
+    int cur_n = 0;
+    int64_t cur_g0 = 0;
+    bool in_batch = false;
+    int64_t batch_idx = 0;   // batches ended; its parity picks the slot of everything kept per two batches
+    bool batch_started = false;
+    hipStream_t last_stream = nullptr;
+    std::vector<void*> allocs;
+    std::vector<void*> host_allocs;
+    // front (rectify .. describe) and back (match .. chain) stages on two streams: batch s's back
+    // waits for its front; batch s's front waits for the back of batch s - 2 (shared ring slots)
+    hipStream_t front_stream = nullptr, back_stream = nullptr;
+    bool front_started = false, back_started = false;
+    hipEvent_t ev_front = nullptr, ev_back[2] = {nullptr, nullptr};
+    bool back_pending[2] = {false, false};
+    // rig pose (tslam_set_rig): E = base_T_rect-left per pair, its inverse, body-frame results
+    bool rig = false;
+    int rig_q = 0, rig_cap = 0;   // E entries set; allocated
+    double* d_rig_E = nullptr;
+    double* d_rig_pose = nullptr;
+    int32_t* d_rig_stats = nullptr;
+    double* d_rig_state = nullptr;
+    // IMU rotation prior for the next batch (tslam_set_motion_prior); the rig's body-frame
+    // version of it (k_rig_prior), per batch parity
+    double* d_prior = nullptr;
+    double* d_rig_prior = nullptr;
+    hipEvent_t ev_prior[2] = {nullptr, nullptr};   // the last reader of each prior slot is done
+    bool prior_read_armed[2] = {false, false};
+    bool prior_armed = false;
+    double* h_prior_pin[2] = {nullptr, nullptr};   // pinned staging of each parity's prior slot
+    bool prior_copy_pending = false;               // copied on the batch's back stream at its first back stage
+    // asynchronous host boundary (tslam_submit_host / tslam_poll_*): the handle's own front/back
+    // streams, pinned staging + device input per batch parity, pinned result slots per parity
+    hipStream_t as_front = nullptr, as_back = nullptr;
+    hipStream_t as_ba = nullptr;      // local BA (ba_window > 0): its own stream on every CU
+    uint8_t* as_stage[2] = {nullptr, nullptr};   // pinned host
+    uint8_t* as_input[2] = {nullptr, nullptr};   // device
+    hipEvent_t as_staged[2] = {nullptr, nullptr};   // DMA out of as_stage[k] done
+    bool as_staged_armed[2] = {false, false};
+    struct ResultSlot {
+        double* pose = nullptr;       // pinned [B][P][68]
+        int32_t* stats = nullptr;     // pinned [B][P][8]
+        double* rig_pose = nullptr;   // pinned [B][68]
+        int32_t* rig_stats = nullptr; // pinned [B][8]
+        std::vector<double> ts;
+        hipEvent_t ev = nullptr;
+        int64_t batch = -1, g0 = 0;
+        int n = 0;
+        bool pending = false;         // completed or in flight, not yet returned by tslam_poll_batch
+    } as_res[2];
+    int64_t as_batches = 0;           // batches submitted through tslam_submit_host
+    int64_t as_last_pose_batch = -1;  // newest batch tslam_poll_pose returned
+    // ---- tslam_api_ba.cpp ----
+    // A8 keyframe window (slots shared by all pairs: keyframes are whole frames)
+    BaStore ba{};
+    int64_t ba_frame[TS_BA_MAXW]{};
+    int64_t ba_nkf = 0;
+    int64_t ba_last = -1;    // newest frame inserted
+    BaTiming ba_timing{};    // k_ba_schur events while profiling is on
+    bool ba_split = false;   // tslam_ba_split_solve: k_ba_reduce + k_ba_solve instead of k_ba_reduce_solve
+    // tslam_ba_defer: a BA stage on its own stream is enqueued later (the next batch's first back
+    // stage, or any call that reads or changes BA state), so the caller's next front stages are on
+    // the GPU before this batch's ~160 BA launches are issued from the host
+    bool ba_defer = false;
+    struct {
+        bool pending = false;
+        BatchCtx c{};
+        hipStream_t s = nullptr;
+        double* snap = nullptr;
+        double* snap_body = nullptr;
+        int32_t* assoc = nullptr;
+        int par = 0;
+    } ba_job;
+    std::map<std::pair<int, int64_t>, std::array<double, 10>> ba_imu;   // (pair, keyframe) -> IMU factor
+    // (pair, keyframe) -> inertial factor record + initial velocity (tslam_ba_inertial_factor)
+    std::map<std::pair<int, int64_t>, std::array<double, TS_BA_INE + 3>> ba_ine;
+    std::vector<std::array<double, 12>> ba_icfg;            // per pair: gravity, bias priors and weights (BaArgs.icfg)
+    std::vector<std::array<uint8_t, TS_BA_MAXW>> ba_ine_slot;   // per pair and slot: carries a factor
+    std::vector<BaArgs> ba_solved;   // per pair: the arguments of its last window solve (replays)
+    // A pair window's keyframe chain (eviction, gate, tiles, iters x (Schur, reduce-and-solve),
+    // back substitution: ~16 launches) replayed from a captured hipGraph per chain shape: the
+    // kernels read a device record (BaRec) written by the graph's first node, so a replay costs one
+    // node update and one graph launch instead of ~16 launches with 2 KB of by-value arguments.
+    // Each shape keeps a ring of instances (own record, event of its last replay), so an instance
+    // is updated only once its previous replay has run.
+    struct BaGraphInst {
+        hipGraph_t graph = nullptr;
+        hipGraphExec_t exec = nullptr;
+        hipGraphNode_t setrec = nullptr;
+        hipEvent_t done = nullptr;
+        bool armed = false;
+        BaRec* d_rec = nullptr;
+    };
+    struct BaGraphSet {
+        std::array<int, 6> key{};   // evict, eviction n_order, n_order, inertial, split, iters
+        std::vector<BaGraphInst> inst;
+        int next = 0;
+    };
+    // tslam_ba_graph: off by default — measured on MI355X (tools/ba_probe.py), a
+    // replay (one node update + the graph launch) costs the host 162 us per keyframe against 80 us
+    // for the 16 direct launches, and the chain's GPU time 0.240 against 0.222 ms
+    bool ba_graph = false;
+    std::vector<BaGraphSet> ba_graphs;
+    hipStream_t ba_cap_stream = nullptr;
+    // BA on its own stream (overlapping the next batch): events per batch parity (batch_idx)
+    hipStream_t ba_stream = nullptr;
+    hipEvent_t ev_fe = nullptr, ev_ba[2] = {nullptr, nullptr};
+    bool ba_pending[2] = {false, false};
+    std::vector<hipEvent_t> ba_events;
+    // ---- tslam_api_exchange.cpp ----
+    // sharded rig (tslam_set_shard): front-end cameras [sh_cam_lo, sh_cam_hi) and back-end frames
+    // [rank * n / world, (rank + 1) * n / world) of every batch
+    int sh_cam_lo = 0, sh_cam_hi = 0, sh_rank = 0, sh_world = 1;
+    // pair split (TSLAM_SHARD_PAIRS, one camera per rank): the back end solves this camera's pair
+    // over half of the batch and the rig pose covers range rig_slot (tslam_ranges.h)
+    bool sh_pairs = false;
+    // library-driven sharding (tslam_comm_init / tslam_group_create, tslam_shard.cpp): the driver
+    // that owns this rank's communicators, streams and exchange buffers (owned here after
+    // tslam_comm_init; a group owns it otherwise)
+    bool sh_comm = false;
+    tslam_shard_driver* drv = nullptr;
+    bool drv_owned = false;
+    // ---- tslam_api_loop.cpp ----
+    // relocalisation map (tslam_map_upload) and scratch
+    double* d_map_xyz = nullptr;
+    uint32_t* d_map_desc = nullptr;
+    int64_t map_n = 0, map_cap = 0;
+    int32_t* d_rl_match = nullptr;
+    double* d_rl_corr = nullptr;
+    int32_t* d_rl_stats = nullptr;
+    double* d_rl_pose = nullptr;
+    double* d_rl_ransac = nullptr;
+    double* d_rl_hyp = nullptr;
+    double* d_rl_rig_pose = nullptr;    // tslam_relocalize_rig: the body record
+    int32_t* d_rl_rig_stats = nullptr;
+    // loop closure (tslam_loop_*): keyframe database, one entry per keyframe, slot = count mod cap
+    int lp_cap = 0, lp_S = 0;
+    int64_t lp_count = 0;
+    double* d_lp_xyz = nullptr;      // [cap][K][3] camera-frame landmarks (compacted)
+    uint32_t* d_lp_desc = nullptr;   // [cap][K][8]
+    int32_t* d_lp_n = nullptr;       // [cap]
+    int32_t* d_lp_votes = nullptr;   // [cap]
+    // asynchronous loop closure (tslam_loop_auto / tslam_loop_job_*): keyframes stored by the
+    // submit path into entry (k mod cap_k) * P + p with a snapshot of their image; jobs (vote,
+    // verify, pose graph) in order on the loop stream, results in pinned memory
+    int lp_auto = 0;                       // keyframe interval (0: off)
+    int64_t* d_lp_pos = nullptr;           // database positions taken so far (device counter)
+    uint32_t* d_lp_snap_kps = nullptr;     // [cap][K][2]
+    int32_t* d_lp_snap_kcount = nullptr;   // [cap][TS_MAX_LEVELS]
+    uint32_t* d_lp_snap_desc = nullptr;    // [cap][K][8]
+    hipStream_t lp_stream = nullptr;
+    hipEvent_t lp_ev_store = nullptr;      // the newest batch's keyframe stores (back stream)
+    bool lp_store_armed = false;
+    struct LoopJob {
+        int kind = 0;                      // 0 free, 1 vote, 2 verify, 3 pose graph
+        int64_t id = 0;
+        hipEvent_t ev = nullptr;
+        int n_out = 0, n_edges = 0;        // votes / nodes; pose-graph edges
+        void* out = nullptr;               // pinned results
+        size_t out_cap = 0;
+        void* in = nullptr;                // pinned pose-graph inputs
+        size_t in_cap = 0;
+        int posted = 0;                    // (worker mutex) 0 queued, 1 on the loop stream, -1 failed
+        std::string err;
+    } lp_jobs[64];
+    int64_t lp_job_next = 1;
+    // the loop worker: a host thread that issues the jobs' copies and launches on the loop stream,
+    // so a job call returns once its inputs are staged (the caller's frame loop does not pay the
+    // ~10-200 launches of a verification or a span solve)
+    struct LoopWorker {
+        std::thread th;
+        std::mutex mu;
+        std::condition_variable cv;
+        std::deque<std::function<void()>> q;
+        int pending = 0;
+        bool stop = false;
+    }* lp_worker = nullptr;
+    // pose graph (tslam_pose_graph) scratch, grown on demand
+    int pg_nodes = 0, pg_edges = 0, pg_np = 0;
+    double *d_pg_T = nullptr, *d_pg_Z = nullptr, *d_pg_info = nullptr, *d_pg_terms = nullptr;
+    double *d_pg_H = nullptr, *d_pg_g = nullptr, *d_pg_delta = nullptr, *d_pg_Ld = nullptr;
+    int32_t *d_pg_edges = nullptr, *d_pg_adj_off = nullptr, *d_pg_adj = nullptr, *d_pg_ftile = nullptr;
+    double* d_pg_cost = nullptr;   // the solve's cost (k_pg_cost_sum), one double
+    // ---- tslam_api_dense.cpp ----
+    // RGB-D dense mapping (tslam_tsdf_*): dense TSDF volume + per-launch pose scratch
+    bool tsdf_on = false;
+    bool tsdf_color = false;          // colour layer (tslam_tsdf_color)
+    TsdfArgs tsdf{};
+    double* d_tsdf_poses = nullptr;   // [TSDF_MAX_FRAMES][TSDF_POSE]
+    double* d_tsdf_wTc = nullptr;     // [TSDF_MAX_FRAMES][16] host poses staged
+    // dense stereo depth (tslam_stereo_depth_*): parameters, output slots and winner-map scratch
+    bool sd_on = false;
+    tslam_stereo_depth_params sd_prm{};
+    int sd_frames = 0;                // slots
+    int sd_w = 0, sd_h = 0;           // image size of the last call (layout of the slots)
+    uint16_t* d_sd_depth = nullptr;   // [sd_frames][H][W]
+    uint16_t* d_sd_disp = nullptr;
+    uint8_t* d_sd_win = nullptr;      // [2][sd_frames][H][W] left / right winners
+    // dense-map outputs (tslam_mesh_* / tslam_esdf_*): scratch sized on first use
+    uint8_t* d_mesh_cfg = nullptr;    // [cubes] configuration bytes
+    uint32_t* d_mesh_bsum = nullptr;  // [blocks] triangle totals
+    uint64_t* d_mesh_boff = nullptr;  // [blocks] first triangle; [blocks] = mesh total
+    size_t mesh_cubes_cap = 0;
+    float* d_mesh_tris = nullptr;     // [tri cap][9]
+    float* d_mesh_cols = nullptr;     // [tri cap][9] vertex colours (colour layer)
+    int64_t mesh_tris_cap = 0, mesh_n = 0;
+    int32_t* d_edt[2] = {nullptr, nullptr};
+    size_t edt_cap = 0;
+    float* d_esdf = nullptr;          // [nz][ny][nx]
+    size_t esdf_cap = 0;
+    bool esdf_valid = false;
+    float* d_dist_tab = nullptr;      // [R^2 + 1]
+    int dist_tab_R = -1;
+    double dist_tab_s = 0.0;
+    uint8_t* d_slice_obs = nullptr;
+    float* d_slice = nullptr;
+    size_t slice_cap = 0;
+};
+
+#define HIPCHK(expr)                                                                           \
+    do {                                                                                       \
+        hipError_t e__ = (expr);                                                               \
+        if (e__ != hipSuccess)                                                                 \
+            return fail(TSLAM_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));      \
+    } while (0)
+
+#define BA_FLUSH(h)                                    \
+    do {                                               \
+        if ((h) && (h)->ba_job.pending) {              \
+            const int rc_flush__ = ba_flush(h);        \
+            if (rc_flush__ != TSLAM_OK) return rc_flush__; \
+        }                                              \
+    } while (0)
+
+// -- tslam_api.cpp ---------------------------------------------------------------------------------
+TSLAM_INTERNAL int fail(int code, const std::string& msg);   // sets tslam_last_error(), returns `code`
+TSLAM_INTERNAL int dev_alloc(tslam_handle* h, void** p, size_t bytes);
+TSLAM_INTERNAL int dev_grow(tslam_handle* h, void** p, size_t need, size_t* cap = nullptr);
+TSLAM_INTERNAL int pinned_reserve(tslam_handle* h, void** p, size_t* cap, size_t bytes);
+TSLAM_INTERNAL BatchCtx make_ctx(tslam_handle* h);
+
+// What differs between the paths in the back stages of a batch: the contexts they run on (null:
+// nothing to run, as on a rank whose frame range is empty) and what TSLAM_STAGE_POSE includes.
+struct BackView {
+    const BatchCtx* b;     // match, refinement and pose
+    const BatchCtx* pre;   // stereo pre-pass of the frame before a sharded range
+    const BatchCtx* rig;   // rig pose
+    bool pose_rig;         // STAGE_POSE runs the rig pose
+    bool pose_chain;       // ... and the chains and the loop database's keyframe store
+};
+// The stage table.  Both return 1 when `stage` was theirs, 0 when it is not one of their codes,
+// < 0 on an error; the caller checks hipGetLastError().
+TSLAM_INTERNAL int run_front_stage(tslam_handle* h, const BatchCtx& c, int stage, hipStream_t s);
+TSLAM_INTERNAL int run_back_stage(tslam_handle* h, const BatchCtx& c, const BackView& v, int stage, hipStream_t s);
+
+// -- tslam_api_ba.cpp ------------------------------------------------------------------------------
+TSLAM_INTERNAL int alloc_ba(tslam_handle* h);
+TSLAM_INTERNAL int ba_flush(tslam_handle* h);
+TSLAM_INTERNAL int ba_stage(tslam_handle* h, const BatchCtx& c, hipStream_t s);    // TSLAM_STAGE_BA
+TSLAM_INTERNAL int ba_inline(tslam_handle* h, const BatchCtx& c, hipStream_t s);   // A8 inside TSLAM_STAGE_ALL
+TSLAM_INTERNAL int ba_reset(tslam_handle* h);
+TSLAM_INTERNAL void ba_destroy(tslam_handle* h);
+
+// -- tslam_api_exchange.cpp ------------------------------------------------------------------------
+TSLAM_INTERNAL int run_sharded_stage(tslam_handle* h, const BatchCtx& c, int stage, hipStream_t s);
+
+// -- tslam_api_loop.cpp ----------------------------------------------------------------------------
+TSLAM_INTERNAL void loop_worker_drain(tslam_handle* h);
+TSLAM_INTERNAL void loop_worker_stop(tslam_handle* h);
+TSLAM_INTERNAL void loop_auto_store(tslam_handle* h, const BatchCtx& c, hipStream_t s);
+TSLAM_INTERNAL int loop_reset(tslam_handle* h);
+TSLAM_INTERNAL void loop_destroy(tslam_handle* h);
+
+// -- tslam_api_dense.cpp ---------------------------------------------------------------------------
+TSLAM_INTERNAL int dense_reset(tslam_handle* h);

@@ -1,5 +1,5 @@
 // tslam_ranges.h — the frame-range arithmetic of a sharded rig, shared by the
-// kernels (k_exchange.hip), the library's host code (tslam_api.cpp, tslam_shard.cpp) and the
+// kernels (k_exchange.hip), the library's host code (tslam_api_exchange.cpp, tslam_shard.cpp) and the
 // sanitizer build of the host code (tests/c/host_check.cpp, `make sanitize`): no HIP dependency.
 //
 // Rank q's back end owns batch frames [q n / world, (q + 1) n / world) of an n-frame batch (any n
