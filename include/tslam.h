@@ -785,10 +785,25 @@ int tslam_esdf_slice(tslam_handle* h, int y0, int y1, double max_dist, double si
  *   image size; either pointer may be NULL.
  * tslam_tsdf_integrate_rect: tslam_tsdf_integrate for depth images that already live in pair
  *   `pair`'s RECTIFIED left camera (what tslam_stereo_depth writes): the voxel's pixel is looked up
- *   directly, not through the raw camera's undistortion table. */
+ *   directly, not through the raw camera's undistortion table.
+ * tslam_stereo_depth_sgm (added within ABI 21: a new symbol, nothing else changes): semi-global
+ *   aggregation (rule 3a of the spec) between the box sums and the winners, opt-in.  enable != 0:
+ *   penalties 0 <= p1 <= p2 <= 2400 in units of the aggregated cost, `paths` a bit mask 1..15
+ *   (1 left->right, 2 right->left, 4 top->bottom, 8 bottom->top), chunk_frames >= 0 frames per
+ *   pass (0: the library chooses: at most max_frames, at most what 1 GiB of scratch holds, at
+ *   least 1; a call's frames are processed in chunks on the one stream), reserved 0.  Scratch is
+ *   2 x n_disp (rounded up to 4) x H x W x 2 bytes per frame of a chunk.  enable == 0 frees the
+ *   scratch and restores the box matcher.  Legal after tslam_stereo_depth_init, outside a batch
+ *   (else TSLAM_ESTATE); a later tslam_stereo_depth_init turns it off again.  tslam_reset keeps
+ *   the setting; tslam_destroy frees the scratch.  While on, tslam_stereo_depth and
+ *   tslam_stereo_depth_images route through it; outputs, slots and _read are unchanged. */
 typedef struct {
     int32_t n_disp, uniqueness, lr_tol, reserved;
 } tslam_stereo_depth_params;
+typedef struct {
+    int32_t enable, p1, p2, paths, chunk_frames, reserved[3];
+} tslam_stereo_depth_sgm_params;
+int tslam_stereo_depth_sgm(tslam_handle* h, const tslam_stereo_depth_sgm_params* params);
 int tslam_stereo_depth_init(tslam_handle* h, const tslam_stereo_depth_params* params, int max_frames);
 int tslam_stereo_depth(tslam_handle* h, int pair, int64_t first_frame, int n_frames, void* stream);
 int tslam_stereo_depth_images(tslam_handle* h, const uint8_t* left, const uint8_t* right, int64_t frame_stride,

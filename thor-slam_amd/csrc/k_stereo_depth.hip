@@ -82,7 +82,11 @@ __device__ __forceinline__ size_t sd_frame_off(const SdArgs& a, int f) {
     return (size_t)(a.ring ? (a.first + f) % a.ring : (int64_t)f) * (size_t)a.stride;
 }
 
-__global__ __launch_bounds__(SD_BLOCK) void k_sd_match(SdArgs a, int nbands) {
+// VOL: the semi-global matcher's first stage (k_sd_sgm.hip).  The same census, cost and box sums,
+// but A(d, y, x) goes to device memory, u16 [n][H][W][pitch] with d contiguous, four d per 8-byte
+// store, and no winner is tracked: the paths cross bands, so the winners come from their sums.
+template <bool VOL>
+__global__ __launch_bounds__(SD_BLOCK) void k_sd_match(SdArgs a, int nbands, uint16_t* vol, int pitch) {
     extern __shared__ __attribute__((aligned(16))) uint8_t sd_lds[];
     const int W = a.W, H = a.H, D = a.D;
     const int rcols = sd_rcols(D), pitch_r = sd_raw_pitch_r(D);
@@ -100,7 +104,8 @@ __global__ __launch_bounds__(SD_BLOCK) void k_sd_match(SdArgs a, int nbands) {
     const uint8_t* R = a.right + fo;
     const size_t out0 = (size_t)f * W * H;
 
-    for (int i = tid; i < SD_TH * SD_RING; i += SD_BLOCK) rb[i] = 0xFFFFFFFFu;
+    if constexpr (!VOL)
+        for (int i = tid; i < SD_TH * SD_RING; i += SD_BLOCK) rb[i] = 0xFFFFFFFFu;
     int flushed = 0;   // right pixels [0, flushed) of the band are written out
 
     for (int xc = 0; xc < W; xc += SD_OUT) {
@@ -146,6 +151,8 @@ __global__ __launch_bounds__(SD_BLOCK) void k_sd_match(SdArgs a, int nbands) {
             m2[k] = c0[k] = c2[k] = p1[k] = p2[k] = SD_BIG;
             prev[k] = 0;
         }
+        uint32_t pk[VOL ? SD_TH : 1][2] = {};   // VOL: A of d & ~3 .. d of each row, packed
+        uint16_t* vcol = VOL ? vol + (out0 + (size_t)y0 * W + cp) * (size_t)pitch : nullptr;
         const int t0 = max(tid - 2, 0), t1 = max(tid - 1, 0), t3 = min(tid + 1, SD_BLOCK - 1), t4 = min(tid + 2, SD_BLOCK - 1);
         for (int d = 0; d < D; ++d) {
             const int xr = cp - d;             // right column of this cost; xr - base >= 0 always
@@ -173,6 +180,17 @@ __global__ __launch_bounds__(SD_BLOCK) void k_sd_match(SdArgs a, int nbands) {
 #pragma unroll
             for (int k = 0; k < SD_TH; ++k) {
                 const int A = (int)((s[k >> 1] >> (16 * (k & 1))) & 0xFFFFu);
+                if constexpr (VOL) {
+                    const uint32_t sh = (uint32_t)A << (16 * (d & 1));
+                    pk[k][0] |= (d & 2) ? 0u : sh;
+                    pk[k][1] |= (d & 2) ? sh : 0u;
+                    if ((d & 3) == 3 || d == D - 1) {   // pitch is a multiple of 4: the store is aligned and inside the cell
+                        if (outcol && y0 + k < H)
+                            *reinterpret_cast<uint2*>(vcol + (size_t)k * W * pitch + (d & ~3)) = make_uint2(pk[k][0], pk[k][1]);
+                        pk[k][0] = pk[k][1] = 0;
+                    }
+                    continue;
+                }
                 // left winner while d ascends: a new strict minimum at d takes the prefix minimum up to
                 // d - 2 as its excluded-neighbour second minimum and A(d - 1) as its left parabola
                 // neighbour; otherwise A is the right neighbour (d == d1 + 1) or joins the second minimum
@@ -190,6 +208,7 @@ __global__ __launch_bounds__(SD_BLOCK) void k_sd_match(SdArgs a, int nbands) {
                     atomicMin(&rb[k * SD_RING + (xr & (SD_RING - 1))], ((uint32_t)A << 8) | (uint32_t)d);
             }
         }
+        if constexpr (VOL) continue;
         if (outcol) {
 #pragma unroll
             for (int k = 0; k < SD_TH; ++k) {
@@ -248,7 +267,7 @@ __global__ __launch_bounds__(256) void k_sd_finish(SdArgs a) {
     a.depth[o] = mm;
 }
 
-hipError_t launch_stereo_depth(const StereoDepthArgs& s, hipStream_t st) {
+static SdArgs sd_args(const StereoDepthArgs& s) {
     SdArgs a;
     a.left = s.left;
     a.right = s.right;
@@ -266,12 +285,36 @@ hipError_t launch_stereo_depth(const StereoDepthArgs& s, hipStream_t st) {
     a.depth = s.depth;
     a.wl = s.win_left;
     a.wr = s.win_right;
-    if (a.n <= 0) return hipSuccess;
+    return a;
+}
+
+template <bool VOL>
+static hipError_t sd_launch_match(const SdArgs& a, uint16_t* vol, int pitch, hipStream_t st) {
     const size_t lds = sd_lds_bytes(a.D);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sd_match), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sd_match<VOL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     const int nbands = (a.H + SD_TH - 1) / SD_TH;
-    hipLaunchKernelGGL(k_sd_match, dim3((unsigned)(a.n * nbands)), dim3(SD_BLOCK), lds, st, a, nbands);
+    hipLaunchKernelGGL(k_sd_match<VOL>, dim3((unsigned)(a.n * nbands)), dim3(SD_BLOCK), lds, st, a, nbands, vol, pitch);
+    return hipGetLastError();
+}
+
+hipError_t launch_stereo_depth(const StereoDepthArgs& s, hipStream_t st) {
+    const SdArgs a = sd_args(s);
+    if (a.n <= 0) return hipSuccess;
+    const hipError_t e = sd_launch_match<false>(a, nullptr, 0, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_sd_finish, dim3((a.W + 255) / 256, a.H, a.n), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_sd_volume(const StereoDepthArgs& s, uint16_t* vol, int pitch, hipStream_t st) {
+    const SdArgs a = sd_args(s);
+    return a.n <= 0 ? hipSuccess : sd_launch_match<true>(a, vol, pitch, st);
+}
+
+hipError_t launch_sd_finish(const StereoDepthArgs& s, hipStream_t st) {
+    const SdArgs a = sd_args(s);
+    if (a.n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_sd_finish, dim3((a.W + 255) / 256, a.H, a.n), dim3(256), 0, st, a);
     return hipGetLastError();
 }

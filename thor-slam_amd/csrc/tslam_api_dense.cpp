@@ -138,6 +138,18 @@ int tslam_tsdf_integrate_rect(tslam_handle* h, int pair, const void* depth, int6
 }
 
 // -- dense stereo depth ------------------------------------------------------------------------------
+// the semi-global matcher's scratch (A and S) goes back to the device; the box matcher runs again
+static void sgm_off(tslam_handle* h) {
+    for (void** p : {(void**)&h->d_sd_vol, (void**)&h->d_sd_sum}) {
+        if (!*p) continue;
+        (void)hipFree(*p);
+        h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), *p), h->allocs.end());
+        *p = nullptr;
+    }
+    h->sd_sgm_on = false;
+    h->sd_sgm_chunk = 0;
+}
+
 int tslam_stereo_depth_init(tslam_handle* h, const tslam_stereo_depth_params* params, int max_frames) {
     if (!h || !params) return fail(TSLAM_EINVAL, "bad argument");
     if (h->prm.rgbd) return fail(TSLAM_ESTATE, "dense stereo depth needs a stereo handle (this one is RGB-D)");
@@ -150,6 +162,7 @@ int tslam_stereo_depth_init(tslam_handle* h, const tslam_stereo_depth_params* pa
     if (max_frames < 1 || max_frames > 65535) return fail(TSLAM_EINVAL, "max_frames must be 1..65535");
     BA_FLUSH(h);
     if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
+    sgm_off(h);   // opt-in per init: n_disp and max_frames size its scratch
     const size_t px = (size_t)max_frames * h->W * h->H;
     int rc = dev_grow(h, (void**)&h->d_sd_depth, 2 * px);
     if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&h->d_sd_disp, 2 * px);
@@ -176,9 +189,65 @@ static int stereo_depth_run(tslam_handle* h, StereoDepthArgs a, void* stream) {
     a.win_right = h->d_sd_win + (size_t)h->sd_frames * h->W * h->H;
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = stream ? (hipStream_t)stream : h->last_stream;
-    HIPCHK(launch_stereo_depth(a, s));
+    if (h->sd_sgm_on) {
+        // chunks of the call's frames, one after the other on the stream, share the scratch
+        const StereoSgmArgs g{h->sd_sgm_prm.p1, h->sd_sgm_prm.p2, h->sd_sgm_prm.paths, h->d_sd_vol, h->d_sd_sum};
+        const size_t px = (size_t)a.W * a.H;
+        for (int f0 = 0; f0 < a.n; f0 += h->sd_sgm_chunk) {
+            StereoDepthArgs c = a;
+            c.n = std::min(h->sd_sgm_chunk, a.n - f0);
+            if (a.ring) c.first = a.first + f0;
+            else {
+                c.left = a.left + (size_t)f0 * a.stride;
+                c.right = a.right + (size_t)f0 * a.stride;
+            }
+            c.depth = a.depth + px * f0;
+            c.disp32 = a.disp32 + px * f0;
+            c.win_left = a.win_left + px * f0;
+            c.win_right = a.win_right + px * f0;
+            HIPCHK(launch_stereo_depth_sgm(c, g, s));
+        }
+    } else {
+        HIPCHK(launch_stereo_depth(a, s));
+    }
     h->sd_w = a.W;
     h->sd_h = a.H;
+    return TSLAM_OK;
+}
+
+int tslam_stereo_depth_sgm(tslam_handle* h, const tslam_stereo_depth_sgm_params* params) {
+    if (!h || !params) return fail(TSLAM_EINVAL, "bad argument");
+    if (!h->sd_on) return fail(TSLAM_ESTATE, "no stereo depth buffers (tslam_stereo_depth_init)");
+    if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_stereo_depth_sgm inside a batch");
+    const tslam_stereo_depth_sgm_params p = *params;
+    if (p.reserved[0] != 0 || p.reserved[1] != 0 || p.reserved[2] != 0) return fail(TSLAM_EINVAL, "reserved must be 0");
+    if (p.enable) {
+        if (p.p1 < 0 || p.p1 > p.p2 || p.p2 > 2400) return fail(TSLAM_EINVAL, "penalties must satisfy 0 <= p1 <= p2 <= 2400");
+        if (p.paths < 1 || p.paths > 15) return fail(TSLAM_EINVAL, "paths must be a bit mask 1..15");
+        if (p.chunk_frames < 0) return fail(TSLAM_EINVAL, "chunk_frames must be >= 0");
+    }
+    BA_FLUSH(h);
+    if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
+    if (!p.enable) {
+        sgm_off(h);
+        return TSLAM_OK;
+    }
+    const size_t frame = (size_t)h->W * h->H * sd_sgm_pitch(h->sd_prm.n_disp) * 2;   // bytes of A (or S) of one frame
+    int chunk = p.chunk_frames;
+    if (chunk == 0) chunk = (int)std::max<size_t>(1, ((size_t)1 << 30) / (2 * frame));
+    chunk = std::min(chunk, h->sd_frames);
+    if (chunk != h->sd_sgm_chunk || !h->d_sd_vol || !h->d_sd_sum) {
+        sgm_off(h);
+        int rc = dev_grow(h, (void**)&h->d_sd_vol, frame * chunk);
+        if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&h->d_sd_sum, frame * chunk);
+        if (rc != TSLAM_OK) {
+            sgm_off(h);
+            return rc;
+        }
+    }
+    h->sd_sgm_prm = p;
+    h->sd_sgm_chunk = chunk;
+    h->sd_sgm_on = true;
     return TSLAM_OK;
 }
 

@@ -320,6 +320,19 @@ struct StereoDepthArgs {
     uint8_t* win_right;
 };
 hipError_t launch_stereo_depth(const StereoDepthArgs& a, hipStream_t s);
+// semi-global aggregation (k_sd_sgm.hip; rule 3a of thor_slam_amd/stereo_depth.py): the same n
+// frames through volume -> path sums -> winners -> k_sd_finish.  vol and sum are scratch, u16
+// [n][H][W][sd_sgm_pitch(n_disp)] each (d contiguous); paths is the bit mask of rule 3a.
+struct StereoSgmArgs {
+    int p1, p2, paths;
+    uint16_t* vol;
+    uint16_t* sum;
+};
+static inline int sd_sgm_pitch(int n_disp) { return (n_disp + 3) & ~3; }
+hipError_t launch_stereo_depth_sgm(const StereoDepthArgs& a, const StereoSgmArgs& g, hipStream_t s);
+// the box matcher's kernels as stages of the semi-global one (k_stereo_depth.hip)
+hipError_t launch_sd_volume(const StereoDepthArgs& a, uint16_t* vol, int pitch, hipStream_t s);
+hipError_t launch_sd_finish(const StereoDepthArgs& a, hipStream_t s);
 // dense-map outputs of the TSDF volume (k_dense.hip): marching-cubes mesh, capped exact ESDF
 struct DenseArgs {
     const float* tsdf;

@@ -249,6 +249,12 @@ struct tslam_handle {
     uint16_t* d_sd_depth = nullptr;   // [sd_frames][H][W]
     uint16_t* d_sd_disp = nullptr;
     uint8_t* d_sd_win = nullptr;      // [2][sd_frames][H][W] left / right winners
+    // semi-global aggregation (tslam_stereo_depth_sgm): off unless asked for
+    bool sd_sgm_on = false;
+    tslam_stereo_depth_sgm_params sd_sgm_prm{};
+    int sd_sgm_chunk = 0;             // frames per pass (resolved from chunk_frames)
+    uint16_t* d_sd_vol = nullptr;     // A [sd_sgm_chunk][H][W][pitch]
+    uint16_t* d_sd_sum = nullptr;     // S, the same layout
     // dense-map outputs (tslam_mesh_* / tslam_esdf_*): scratch sized on first use
     uint8_t* d_mesh_cfg = nullptr;    // [cubes] configuration bytes
     uint32_t* d_mesh_bsum = nullptr;  // [blocks] triangle totals

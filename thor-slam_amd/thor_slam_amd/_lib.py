@@ -93,6 +93,14 @@ class ImuStep(ctypes.Structure):
     ]
 
 
+class StereoDepthSgmParams(ctypes.Structure):
+    """tslam_stereo_depth_sgm_params: semi-global aggregation of the dense stereo matcher."""
+    _fields_ = [
+        ("enable", ctypes.c_int32), ("p1", ctypes.c_int32), ("p2", ctypes.c_int32), ("paths", ctypes.c_int32),
+        ("chunk_frames", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3),
+    ]
+
+
 def camera_desc(cam) -> CameraDesc:
     """A ``CameraConfig`` (intrinsics + world extrinsics) as a ``tslam_camera_desc``."""
     d = CameraDesc()
@@ -260,6 +268,7 @@ _SIGNATURES = {
     "tslam_stereo_depth_buffers": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
                                                   ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64)]),
     "tslam_stereo_depth_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "tslam_stereo_depth_sgm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "tslam_tsdf_integrate_rect": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
                                                  ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
 }
@@ -888,6 +897,13 @@ class Handle:
         prm = (ctypes.c_int32 * 4)(int(n_disp), int(uniqueness), int(lr_tol), 0)
         _check(self.lib.tslam_stereo_depth_init(self.h, ctypes.addressof(prm), int(max_frames)))
         self._sd_shape = (self.height, self.width)
+
+    def stereo_depth_sgm(self, p1: int = 100, p2: int = 1200, paths: int = 15, enable: bool = True,
+                         chunk_frames: int = 0) -> None:
+        """Semi-global aggregation (rule 3a) on or off, after ``stereo_depth_init`` (which turns it
+        off again); ``chunk_frames`` 0 lets the library size its scratch."""
+        prm = StereoDepthSgmParams(int(bool(enable)), int(p1), int(p2), int(paths), int(chunk_frames), (ctypes.c_int32 * 3)())
+        _check(self.lib.tslam_stereo_depth_sgm(self.h, ctypes.addressof(prm)))
 
     def stereo_depth(self, first_frame: int, n_frames: int, pair: int = 0, stream: int = 0) -> None:
         """Depth of ``pair``'s frames first_frame.. of the last batch into slots 0..n_frames-1."""

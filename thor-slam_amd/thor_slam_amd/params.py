@@ -12,6 +12,7 @@ from dataclasses import dataclass
 
 from .slam.interface import SlamConfig
 from .stereo_depth import check_params as check_stereo_depth_params
+from .stereo_depth import check_sgm_params as check_stereo_depth_sgm_params
 
 # Upper bounds baked into the kernels (checked on the host before any launch).
 MAX_WIDTH = 2047
@@ -144,6 +145,12 @@ class HipSlamConfig(SlamConfig):
     stereo_depth_uniqueness: int = 10   # percent: best cost <= (100 - u) % of the best non-neighbour
     stereo_depth_lr_tol: int = 1        # px, left-right consistency
     stereo_depth_interval: int = 1
+    # semi-global aggregation over four paths between the box sums and the winners (rule 3a of
+    # thor_slam_amd/stereo_depth.py): fills weakly textured surfaces; penalties in units of the
+    # aggregated cost, 0 <= p1 <= p2 <= 2400
+    stereo_depth_sgm: bool = False
+    stereo_depth_p1: int = 100
+    stereo_depth_p2: int = 1200
     # pipeline
     batch_size: int = 1             # frames per submission
     sync: bool = False              # wait for every batch before process_frames returns (latency mode)
@@ -177,6 +184,9 @@ class HipSlamConfig(SlamConfig):
         check_stereo_depth_params(0, self.stereo_depth_uniqueness, self.stereo_depth_lr_tol)
         if self.stereo_depth_interval < 1:
             raise ValueError("stereo_depth_interval must be >= 1")
+        check_stereo_depth_sgm_params(self.stereo_depth_p1, self.stereo_depth_p2)
+        if self.stereo_depth_sgm and not self.stereo_depth:
+            raise ValueError("stereo_depth_sgm needs stereo_depth=True")
         if self.dense_map:
             if not (self.rgbd or self.stereo_depth):
                 raise ValueError("dense_map needs depth: rgbd=True (depth input) or stereo_depth=True (stereo rig)")

@@ -521,6 +521,8 @@ class HipSlamEngine(SlamEngine):
                 if cfg.stereo_depth:   # a stereo rig: pair 0's depth comes from the dense matcher
                     self._handle.stereo_depth_init(max_frames=cfg.batch_size, uniqueness=cfg.stereo_depth_uniqueness,
                                                    lr_tol=cfg.stereo_depth_lr_tol)
+                    if cfg.stereo_depth_sgm:
+                        self._handle.stereo_depth_sgm(p1=cfg.stereo_depth_p1, p2=cfg.stereo_depth_p2)
             self._sd_last = None   # (slot, timestamp) of the newest stereo depth image
             self._loop = None
             if cfg.enable_loop_closure and cfg.devices and cfg.rgbd:

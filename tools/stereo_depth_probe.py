@@ -1,6 +1,7 @@
 """Time the dense stereo matcher (tslam_stereo_depth, k_stereo_depth.hip) on resident data.
 
     python tools/stereo_depth_probe.py [--frames 64] [--disp 128] [--reps 10] [--out profiles/stereo_depth_c2.json]
+    python tools/stereo_depth_probe.py --sgm [--p1 100] [--p2 1200] [--out profiles/stereo_depth_sgm_c2.json]
 
 C2 geometry by default (640x400, one pair, D = 128, 64 frames resident in the ring).  One batch is
 tracked first so the ring holds rectified images; after a warm-up launch the matcher runs `reps`
@@ -9,6 +10,12 @@ times k_detect alone (inside a batch, also between events) over the same frames.
 frame are what the algorithm must move (both images read once, depth + disp32 written, the two u8
 winner maps written and read once); (x, d) cells = W * H * D per frame.  Needs the GPU: there is
 no fallback.
+
+With --sgm the same run then turns semi-global aggregation on (tslam_stereo_depth_sgm, k_sd_sgm.hip)
+and times it the same way on the same frames, so both figures come from one session.  Its bytes per
+frame are what its stages must move through device memory: the volume A (u16, W * H * D cells)
+written once, read by each of the four path passes and not again; S written by the first pass, read
+and written by the other three, read by the winners; plus the box matcher's images and outputs.
 """
 
 from __future__ import annotations
@@ -32,6 +39,9 @@ def main() -> None:
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=400)
+    ap.add_argument("--sgm", action="store_true", help="also time semi-global aggregation on the same input")
+    ap.add_argument("--p1", type=int, default=100)
+    ap.add_argument("--p2", type=int, default=1200)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     import torch
@@ -74,6 +84,29 @@ def main() -> None:
     depth, disp32 = h.stereo_depth_read(B - 1)
     valid = float((depth > 0).mean())
 
+    sgm = None
+    if args.sgm:
+        h.stereo_depth_sgm(p1=args.p1, p2=args.p2)
+        timed(run, 2)
+        sgm_trials = [timed(run, args.reps) for _ in range(3)]
+        sgm_valid = float((h.stereo_depth_read(B - 1)[0] > 0).mean())
+        h.stereo_depth_sgm(enable=False)
+        cells = W * H * ((D + 3) & ~3)
+        vol_bytes = 2 * cells * (1 + 4)                 # A: written, read by 4 passes
+        sum_bytes = 2 * cells * (1 + 3 * 2 + 1)         # S: written, 3 x (read + written), read by the winners
+        sgm_bytes = 2 * W * H + 2 * 2 * W * H + 2 * 2 * W * H + vol_bytes + sum_bytes
+        sgm_us = min(sgm_trials) / B
+        sgm = {
+            "p1": args.p1, "p2": args.p2, "paths": 15,
+            "us_per_batch_trials": [round(t, 1) for t in sgm_trials],
+            "us_per_frame": round(sgm_us, 2),
+            "bytes_per_frame": sgm_bytes,
+            "achieved_GBps": round(sgm_bytes / sgm_us / 1e3, 2),
+            "share_of_8TBps_peak": round(sgm_bytes / sgm_us / 1e6 / HBM_PEAK_TBS, 5),
+            "over_box_matcher": round(min(sgm_trials) / us_batch, 2),
+            "valid_fraction_last_frame": round(sgm_valid, 4),
+        }
+
     h.begin_batch(dev.data_ptr(), B)
     h.run_kernel("rectify_pyramid", s)
     timed(lambda: h.run_kernel("detect", s), 2)
@@ -98,6 +131,8 @@ def main() -> None:
         "k_detect_us_per_frame_both_cameras": round(min(det_trials) / B, 3),
         "stereo_depth_over_k_detect": round(us_batch / min(det_trials), 1),
     }
+    if sgm is not None:
+        out["sgm"] = sgm
     line = json.dumps(out)
     print(line)
     if args.out:
