@@ -796,7 +796,23 @@ int tslam_esdf_slice(tslam_handle* h, int y0, int y1, double max_dist, double si
  *   scratch and restores the box matcher.  Legal after tslam_stereo_depth_init, outside a batch
  *   (else TSLAM_ESTATE); a later tslam_stereo_depth_init turns it off again.  tslam_reset keeps
  *   the setting; tslam_destroy frees the scratch.  While on, tslam_stereo_depth and
- *   tslam_stereo_depth_images route through it; outputs, slots and _read are unchanged. */
+ *   tslam_stereo_depth_images route through it; outputs, slots and _read are unchanged.
+ * tslam_stereo_depth_filter (added within ABI 21: two new symbols, nothing else changes): the
+ *   post-filters of the disparity map (rules 9 and 10 of the spec), opt-in, after the box matcher
+ *   and after semi-global aggregation alike.  enable != 0: `median` 0 (off), 3, 5 or 7, the lower
+ *   median of the window's valid values at every valid pixel (it never changes which pixels are
+ *   valid); `speckle_size` 0 (off) .. 65535 and `speckle_range` 0 .. 8191 (1/32 px): 4-connected
+ *   components of valid pixels whose neighbours differ by at most the range are zeroed where they
+ *   have at most speckle_size pixels; one of median and speckle_size must be non-zero; reserved 0.
+ *   The median runs first; depth is computed from the filtered disp32.  The speckle filter takes
+ *   8 bytes per pixel of every slot.  enable == 0 frees that and restores the unfiltered output.
+ *   Same life cycle as tslam_stereo_depth_sgm and independent of it, in either order: legal after
+ *   tslam_stereo_depth_init, outside a batch (else TSLAM_ESTATE); a later tslam_stereo_depth_init
+ *   turns it off; tslam_reset keeps it; tslam_destroy frees it.  A refused call changes nothing.
+ * tslam_stereo_depth_filter_apply: the enabled filters and the depth on caller-supplied dense
+ *   device planes of disp32, u16 [n_frames][height][width] (16 .. the handle's size each; values
+ *   above 8191 count as 8191), into slots 0 .. n_frames - 1: a disparity from elsewhere is cleaned
+ *   this way.  TSLAM_ESTATE unless the filters are on. */
 typedef struct {
     int32_t n_disp, uniqueness, lr_tol, reserved;
 } tslam_stereo_depth_params;
@@ -804,6 +820,12 @@ typedef struct {
     int32_t enable, p1, p2, paths, chunk_frames, reserved[3];
 } tslam_stereo_depth_sgm_params;
 int tslam_stereo_depth_sgm(tslam_handle* h, const tslam_stereo_depth_sgm_params* params);
+typedef struct {
+    int32_t enable, median, speckle_size, speckle_range, reserved[4];
+} tslam_stereo_depth_filter_params;
+int tslam_stereo_depth_filter(tslam_handle* h, const tslam_stereo_depth_filter_params* params);
+int tslam_stereo_depth_filter_apply(tslam_handle* h, const uint16_t* disp32, int width, int height, double fxb,
+                                    int n_frames, void* stream);
 int tslam_stereo_depth_init(tslam_handle* h, const tslam_stereo_depth_params* params, int max_frames);
 int tslam_stereo_depth(tslam_handle* h, int pair, int64_t first_frame, int n_frames, void* stream);
 int tslam_stereo_depth_images(tslam_handle* h, const uint8_t* left, const uint8_t* right, int64_t frame_stride,

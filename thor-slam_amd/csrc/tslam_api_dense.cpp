@@ -150,6 +150,17 @@ static void sgm_off(tslam_handle* h) {
     h->sd_sgm_chunk = 0;
 }
 
+// the speckle filter's label and count planes go back to the device; the matcher's output is final again
+static void filter_off(tslam_handle* h) {
+    for (void** p : {(void**)&h->d_sd_label, (void**)&h->d_sd_count}) {
+        if (!*p) continue;
+        (void)hipFree(*p);
+        h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), *p), h->allocs.end());
+        *p = nullptr;
+    }
+    h->sd_flt_on = false;
+}
+
 int tslam_stereo_depth_init(tslam_handle* h, const tslam_stereo_depth_params* params, int max_frames) {
     if (!h || !params) return fail(TSLAM_EINVAL, "bad argument");
     if (h->prm.rgbd) return fail(TSLAM_ESTATE, "dense stereo depth needs a stereo handle (this one is RGB-D)");
@@ -163,6 +174,7 @@ int tslam_stereo_depth_init(tslam_handle* h, const tslam_stereo_depth_params* pa
     BA_FLUSH(h);
     if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
     sgm_off(h);   // opt-in per init: n_disp and max_frames size its scratch
+    filter_off(h);
     const size_t px = (size_t)max_frames * h->W * h->H;
     int rc = dev_grow(h, (void**)&h->d_sd_depth, 2 * px);
     if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&h->d_sd_disp, 2 * px);
@@ -176,6 +188,15 @@ int tslam_stereo_depth_init(tslam_handle* h, const tslam_stereo_depth_params* pa
     h->sd_w = h->W;
     h->sd_h = h->H;
     h->sd_on = true;
+    return TSLAM_OK;
+}
+
+// rules 9 and 10, then rule 8, on the n frames of W x H that lie in the slots
+static int stereo_filter_run(tslam_handle* h, int W, int H, int n, double fxb, hipStream_t s) {
+    const tslam_stereo_depth_filter_params& p = h->sd_flt_prm;
+    const StereoFilterArgs f{W, H, n, fxb, p.median, p.speckle_size, p.speckle_range, h->d_sd_disp, h->d_sd_depth,
+                             reinterpret_cast<uint16_t*>(h->d_sd_win), h->d_sd_label, h->d_sd_count};
+    HIPCHK(launch_sd_filter(f, s));
     return TSLAM_OK;
 }
 
@@ -210,6 +231,8 @@ static int stereo_depth_run(tslam_handle* h, StereoDepthArgs a, void* stream) {
     } else {
         HIPCHK(launch_stereo_depth(a, s));
     }
+    if (h->sd_flt_on)
+        if (const int rc = stereo_filter_run(h, a.W, a.H, a.n, a.fxb, s); rc != TSLAM_OK) return rc;
     h->sd_w = a.W;
     h->sd_h = a.H;
     return TSLAM_OK;
@@ -248,6 +271,63 @@ int tslam_stereo_depth_sgm(tslam_handle* h, const tslam_stereo_depth_sgm_params*
     h->sd_sgm_prm = p;
     h->sd_sgm_chunk = chunk;
     h->sd_sgm_on = true;
+    return TSLAM_OK;
+}
+
+int tslam_stereo_depth_filter(tslam_handle* h, const tslam_stereo_depth_filter_params* params) {
+    if (!h || !params) return fail(TSLAM_EINVAL, "bad argument");
+    if (!h->sd_on) return fail(TSLAM_ESTATE, "no stereo depth buffers (tslam_stereo_depth_init)");
+    if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_stereo_depth_filter inside a batch");
+    const tslam_stereo_depth_filter_params p = *params;
+    if (p.reserved[0] != 0 || p.reserved[1] != 0 || p.reserved[2] != 0 || p.reserved[3] != 0)
+        return fail(TSLAM_EINVAL, "reserved must be 0");
+    if (p.enable) {
+        if (p.median != 0 && p.median != 3 && p.median != 5 && p.median != 7) return fail(TSLAM_EINVAL, "median must be 0, 3, 5 or 7");
+        if (p.speckle_size < 0 || p.speckle_size > 65535) return fail(TSLAM_EINVAL, "speckle_size must be 0..65535");
+        if (p.speckle_range < 0 || p.speckle_range > 8191) return fail(TSLAM_EINVAL, "speckle_range must be 0..8191");
+        if (p.median == 0 && p.speckle_size == 0) return fail(TSLAM_EINVAL, "enable needs a median or a speckle size");
+    }
+    BA_FLUSH(h);
+    if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
+    if (!p.enable) {
+        filter_off(h);
+        return TSLAM_OK;
+    }
+    if (p.speckle_size == 0) {
+        filter_off(h);   // the median needs no planes of its own
+    } else if (!h->d_sd_label || !h->d_sd_count) {
+        const bool was_on = h->sd_flt_on;
+        const size_t bytes = sizeof(uint32_t) * h->sd_frames * h->W * h->H;
+        int rc = dev_grow(h, (void**)&h->d_sd_label, bytes);
+        if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&h->d_sd_count, bytes);
+        if (rc != TSLAM_OK) {
+            filter_off(h);
+            h->sd_flt_on = was_on;   // a median-only setting needs none of what failed
+            return rc;
+        }
+    }
+    h->sd_flt_prm = p;
+    h->sd_flt_on = true;
+    return TSLAM_OK;
+}
+
+int tslam_stereo_depth_filter_apply(tslam_handle* h, const uint16_t* disp32, int width, int height, double fxb, int n_frames,
+                                    void* stream) {
+    if (!h || !disp32) return fail(TSLAM_EINVAL, "bad argument");
+    if (!h->sd_on) return fail(TSLAM_ESTATE, "no stereo depth buffers (tslam_stereo_depth_init)");
+    if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_stereo_depth_filter_apply inside a batch");
+    if (!h->sd_flt_on) return fail(TSLAM_ESTATE, "the filters are off (tslam_stereo_depth_filter)");
+    if (n_frames < 0 || n_frames > h->sd_frames) return fail(TSLAM_EINVAL, "n_frames must be 0..max_frames");
+    if (width < 16 || height < 16 || width > h->W || height > h->H)
+        return fail(TSLAM_EINVAL, "width / height must be 16 .. the handle's size");
+    if (!(fxb > 0.0)) return fail(TSLAM_EINVAL, "fxb must be > 0");
+    BA_FLUSH(h);
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = stream ? (hipStream_t)stream : h->last_stream;
+    HIPCHK(launch_sd_filter_load(disp32, h->d_sd_disp, (size_t)n_frames * width * height, s));
+    if (const int rc = stereo_filter_run(h, width, height, n_frames, fxb, s); rc != TSLAM_OK) return rc;
+    h->sd_w = width;
+    h->sd_h = height;
     return TSLAM_OK;
 }
 

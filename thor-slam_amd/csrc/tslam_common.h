@@ -333,6 +333,23 @@ hipError_t launch_stereo_depth_sgm(const StereoDepthArgs& a, const StereoSgmArgs
 // the box matcher's kernels as stages of the semi-global one (k_stereo_depth.hip)
 hipError_t launch_sd_volume(const StereoDepthArgs& a, uint16_t* vol, int pitch, hipStream_t s);
 hipError_t launch_sd_finish(const StereoDepthArgs& a, hipStream_t s);
+// post-filters (k_sd_filter.hip; rules 9 and 10 of thor_slam_amd/stereo_depth.py) on n dense frames
+// of disp32, in place, then rule 8's depth.  median 0 / 3 / 5 / 7, speckle_size 0 = off.  tmp: u16
+// [n][H][W], the median's output (unused without it); label, count: u32 [n][H][W] each (unused
+// without the speckle filter).
+struct StereoFilterArgs {
+    int W, H, n;
+    double fxb;
+    int median, speckle_size, speckle_range;
+    uint16_t* disp32;
+    uint16_t* depth;
+    uint16_t* tmp;
+    uint32_t* label;
+    uint32_t* count;
+};
+hipError_t launch_sd_filter(const StereoFilterArgs& a, hipStream_t s);
+// n values of a caller's disp32 plane into dst, clamped to 8191
+hipError_t launch_sd_filter_load(const uint16_t* src, uint16_t* dst, size_t n, hipStream_t s);
 // dense-map outputs of the TSDF volume (k_dense.hip): marching-cubes mesh, capped exact ESDF
 struct DenseArgs {
     const float* tsdf;

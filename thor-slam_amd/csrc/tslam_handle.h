@@ -255,6 +255,12 @@ struct tslam_handle {
     int sd_sgm_chunk = 0;             // frames per pass (resolved from chunk_frames)
     uint16_t* d_sd_vol = nullptr;     // A [sd_sgm_chunk][H][W][pitch]
     uint16_t* d_sd_sum = nullptr;     // S, the same layout
+    // median and speckle filters (tslam_stereo_depth_filter): off unless asked for.  The median
+    // writes into d_sd_win, whose winner maps are dead by then and which is one u16 plane per slot
+    bool sd_flt_on = false;
+    tslam_stereo_depth_filter_params sd_flt_prm{};
+    uint32_t* d_sd_label = nullptr;   // [sd_frames][H][W], with a speckle size only
+    uint32_t* d_sd_count = nullptr;
     // dense-map outputs (tslam_mesh_* / tslam_esdf_*): scratch sized on first use
     uint8_t* d_mesh_cfg = nullptr;    // [cubes] configuration bytes
     uint32_t* d_mesh_bsum = nullptr;  // [blocks] triangle totals

@@ -101,6 +101,14 @@ class StereoDepthSgmParams(ctypes.Structure):
     ]
 
 
+class StereoDepthFilterParams(ctypes.Structure):
+    """tslam_stereo_depth_filter_params: median and speckle filters of the dense stereo matcher."""
+    _fields_ = [
+        ("enable", ctypes.c_int32), ("median", ctypes.c_int32), ("speckle_size", ctypes.c_int32),
+        ("speckle_range", ctypes.c_int32), ("reserved", ctypes.c_int32 * 4),
+    ]
+
+
 def camera_desc(cam) -> CameraDesc:
     """A ``CameraConfig`` (intrinsics + world extrinsics) as a ``tslam_camera_desc``."""
     d = CameraDesc()
@@ -269,6 +277,9 @@ _SIGNATURES = {
                                                   ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64)]),
     "tslam_stereo_depth_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "tslam_stereo_depth_sgm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "tslam_stereo_depth_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "tslam_stereo_depth_filter_apply": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                       ctypes.c_double, ctypes.c_int, ctypes.c_void_p]),
     "tslam_tsdf_integrate_rect": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
                                                  ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
 }
@@ -904,6 +915,21 @@ class Handle:
         off again); ``chunk_frames`` 0 lets the library size its scratch."""
         prm = StereoDepthSgmParams(int(bool(enable)), int(p1), int(p2), int(paths), int(chunk_frames), (ctypes.c_int32 * 3)())
         _check(self.lib.tslam_stereo_depth_sgm(self.h, ctypes.addressof(prm)))
+
+    def stereo_depth_filter(self, median: int = 5, speckle_size: int = 50, speckle_range: int = 32, enable: bool = True) -> None:
+        """The median (rule 9) and speckle (rule 10) filters on or off, after ``stereo_depth_init``
+        (which turns them off again); independent of ``stereo_depth_sgm``."""
+        prm = StereoDepthFilterParams(int(bool(enable)), int(median), int(speckle_size), int(speckle_range),
+                                      (ctypes.c_int32 * 4)())
+        _check(self.lib.tslam_stereo_depth_filter(self.h, ctypes.addressof(prm)))
+
+    def stereo_depth_filter_apply(self, disp32_dev_ptr: int, width: int, height: int, fxb: float, n_frames: int,
+                                  stream: int = 0) -> None:
+        """The enabled filters and the depth on caller-supplied dense device planes of disp32 (u16
+        [n_frames][height][width]) into slots 0..n_frames-1."""
+        _check(self.lib.tslam_stereo_depth_filter_apply(self.h, ctypes.c_void_p(disp32_dev_ptr), int(width), int(height),
+                                                        float(fxb), int(n_frames), ctypes.c_void_p(stream)))
+        self._sd_shape = (int(height), int(width))
 
     def stereo_depth(self, first_frame: int, n_frames: int, pair: int = 0, stream: int = 0) -> None:
         """Depth of ``pair``'s frames first_frame.. of the last batch into slots 0..n_frames-1."""

@@ -12,6 +12,7 @@ from dataclasses import dataclass
 
 from .slam.interface import SlamConfig
 from .stereo_depth import check_params as check_stereo_depth_params
+from .stereo_depth import check_filter_params as check_stereo_depth_filter_params
 from .stereo_depth import check_sgm_params as check_stereo_depth_sgm_params
 
 # Upper bounds baked into the kernels (checked on the host before any launch).
@@ -151,6 +152,12 @@ class HipSlamConfig(SlamConfig):
     stereo_depth_sgm: bool = False
     stereo_depth_p1: int = 100
     stereo_depth_p2: int = 1200
+    # post-filters of the disparity map (rules 9 and 10 of thor_slam_amd/stereo_depth.py), off at 0:
+    # the lower median of a 3 / 5 / 7 window's valid values, then 4-connected components of at most
+    # stereo_depth_speckle_size pixels (neighbours within stereo_depth_speckle_range / 32 px) removed
+    stereo_depth_median: int = 0
+    stereo_depth_speckle_size: int = 0
+    stereo_depth_speckle_range: int = 32
     # pipeline
     batch_size: int = 1             # frames per submission
     sync: bool = False              # wait for every batch before process_frames returns (latency mode)
@@ -187,6 +194,9 @@ class HipSlamConfig(SlamConfig):
         check_stereo_depth_sgm_params(self.stereo_depth_p1, self.stereo_depth_p2)
         if self.stereo_depth_sgm and not self.stereo_depth:
             raise ValueError("stereo_depth_sgm needs stereo_depth=True")
+        check_stereo_depth_filter_params(self.stereo_depth_median, self.stereo_depth_speckle_size, self.stereo_depth_speckle_range)
+        if (self.stereo_depth_median or self.stereo_depth_speckle_size) and not self.stereo_depth:
+            raise ValueError("stereo_depth_median / stereo_depth_speckle_size need stereo_depth=True")
         if self.dense_map:
             if not (self.rgbd or self.stereo_depth):
                 raise ValueError("dense_map needs depth: rgbd=True (depth input) or stereo_depth=True (stereo rig)")

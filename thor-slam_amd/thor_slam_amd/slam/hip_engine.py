@@ -523,6 +523,9 @@ class HipSlamEngine(SlamEngine):
                                                    lr_tol=cfg.stereo_depth_lr_tol)
                     if cfg.stereo_depth_sgm:
                         self._handle.stereo_depth_sgm(p1=cfg.stereo_depth_p1, p2=cfg.stereo_depth_p2)
+                    if cfg.stereo_depth_median or cfg.stereo_depth_speckle_size:
+                        self._handle.stereo_depth_filter(median=cfg.stereo_depth_median, speckle_size=cfg.stereo_depth_speckle_size,
+                                                         speckle_range=cfg.stereo_depth_speckle_range)
             self._sd_last = None   # (slot, timestamp) of the newest stereo depth image
             self._loop = None
             if cfg.enable_loop_closure and cfg.devices and cfg.rgbd:

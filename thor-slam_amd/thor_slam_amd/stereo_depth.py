@@ -43,8 +43,25 @@ Parameters: n_disp D (candidates 0..D-1, 4..256), uniqueness u (0..99), lr_tol (
 8. Depth: mm = floor((fxb * 32000.0) / (double) disp32 + 0.5) (f64: one multiply, one divide, one
    add, in that order); depth = mm as u16, or 0 where the pixel is invalid or mm > 65535.
 
-Out of scope: 8 or 16 aggregation paths, median and speckle filters, matching on a coarser
-pyramid level, a colour layer from the gray images; the engine integrates pair 0 only (the C ABI
+Post-filters (opt-in; ``csrc/k_sd_filter.hip``, restated in ``tests/ref_stereo_filter.py``).  Both
+act on disp32 after rule 7, i.e. after the left-right check (u16, 0 = invalid, <= 8176), after the
+box matcher and after rule 3a alike; rule 9 first, then rule 10; rule 8 is then computed from the
+filtered disp32.
+
+9. Median.  Parameter m in {0 (off), 3, 5, 7}.  A pixel with disp32 = 0 stays 0.  For a valid
+   pixel, take the m x m window centred on it, window coordinates clamped to the image (a clamped
+   position counts as often as it occurs), and let v_0 <= ... <= v_(n-1) be the non-zero values in
+   it (n >= 1: the centre is one of them).  The output is v at index floor((n - 1) / 2), the lower
+   median.  All outputs are computed from the unfiltered input.  The rule never changes which
+   pixels are valid: a median that treats 0 as a value invents disparities across holes.
+10. Speckle.  Parameters ``speckle_size`` s, 0 (off) .. 65535, and ``speckle_range`` r, 0 .. 8191
+   in disp32 units (default 32 = 1 px).  Two 4-neighbours are linked iff both are non-zero and
+   |a - b| <= r.  Components are the transitive closure of the links (the ends of a ramp may differ
+   by far more than r).  Every pixel of a component with at most s pixels becomes 0.  The result
+   depends on the partition alone, so every labelling algorithm gives the same bits.
+
+Out of scope: 8 or 16 aggregation paths, 8-connected speckles, temporal, edge-preserving and
+hole-filling filters, filtering depth rather than disparity, matching on a coarser pyramid level, a colour layer from the gray images; the engine integrates pair 0 only (the C ABI
 takes any pair) and does not run on sharded rigs.
 """
 
@@ -65,6 +82,22 @@ SGM_P_MAX = 2400
 SGM_DEFAULT_P1, SGM_DEFAULT_P2 = 100, 1200
 SGM_PATH_LR, SGM_PATH_RL, SGM_PATH_TB, SGM_PATH_BT = 1, 2, 4, 8
 SGM_PATHS_ALL = 15
+
+
+# rules 9 and 10
+MEDIAN_SIZES = (0, 3, 5, 7)
+SPECKLE_SIZE_MAX = 65535
+SPECKLE_RANGE_MAX = 8191
+DEFAULT_SPECKLE_RANGE = 32
+
+
+def check_filter_params(median: int, speckle_size: int, speckle_range: int = DEFAULT_SPECKLE_RANGE) -> None:
+    if median not in MEDIAN_SIZES:
+        raise ValueError(f"median must be one of {MEDIAN_SIZES}")
+    if not 0 <= speckle_size <= SPECKLE_SIZE_MAX:
+        raise ValueError(f"speckle_size must be in [0, {SPECKLE_SIZE_MAX}]")
+    if not 0 <= speckle_range <= SPECKLE_RANGE_MAX:
+        raise ValueError(f"speckle_range must be in [0, {SPECKLE_RANGE_MAX}]")
 
 
 def check_params(n_disp: int, uniqueness: int, lr_tol: int) -> None:

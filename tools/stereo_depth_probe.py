@@ -2,6 +2,7 @@
 
     python tools/stereo_depth_probe.py [--frames 64] [--disp 128] [--reps 10] [--out profiles/stereo_depth_c2.json]
     python tools/stereo_depth_probe.py --sgm [--p1 100] [--p2 1200] [--out profiles/stereo_depth_sgm_c2.json]
+    python tools/stereo_depth_probe.py --filter [--median 5] [--speckle-size 50] [--out profiles/stereo_depth_filter_c2.json]
 
 C2 geometry by default (640x400, one pair, D = 128, 64 frames resident in the ring).  One batch is
 tracked first so the ring holds rectified images; after a warm-up launch the matcher runs `reps`
@@ -16,6 +17,15 @@ and times it the same way on the same frames, so both figures come from one sess
 frame are what its stages must move through device memory: the volume A (u16, W * H * D cells)
 written once, read by each of the four path passes and not again; S written by the first pass, read
 and written by the other three, read by the winners; plus the box matcher's images and outputs.
+
+With --filter the same run then turns the post-filters on (tslam_stereo_depth_filter, k_sd_filter.hip)
+in three settings, the median alone, the speckle filter alone and both, and times the matcher with
+them the same way on the same frames: the filter stage is the difference to the box matcher's time
+of this session.  As a cross-check the stage is also timed on its own through
+tslam_stereo_depth_filter_apply on the unfiltered disp32 (that route adds a clamping copy).  Its
+bytes per frame are what its launches must move: 2 B read and 2 B written per pixel by the median,
+the labelling's 2 B read and 8 B written, 4 B read by the sum, 6 B read and 4 B written by the last
+pass, which also writes the depth.
 """
 
 from __future__ import annotations
@@ -42,8 +52,13 @@ def main() -> None:
     ap.add_argument("--sgm", action="store_true", help="also time semi-global aggregation on the same input")
     ap.add_argument("--p1", type=int, default=100)
     ap.add_argument("--p2", type=int, default=1200)
+    ap.add_argument("--filter", action="store_true", help="also time the median and speckle filters on the same input")
+    ap.add_argument("--median", type=int, default=5)
+    ap.add_argument("--speckle-size", type=int, default=50)
+    ap.add_argument("--speckle-range", type=int, default=32)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    import numpy as np
     import torch
 
     from thor_slam_amd._lib import Handle
@@ -107,6 +122,39 @@ def main() -> None:
             "valid_fraction_last_frame": round(sgm_valid, 4),
         }
 
+    flt = None
+    if args.filter:
+        px = W * H
+        settings = {   # name -> (median, speckle_size, bytes per pixel that must move)
+            "median": (args.median, 0, 2 + 2 + 2 + 2 + 2),              # disp32 -> median; median -> disp32, depth
+            "speckle": (0, args.speckle_size, 2 + 8 + 4 + 2 + 4 + 4),   # label: read, label + count; sum: count; apply: disp32, label -> disp32, depth
+            "both": (args.median, args.speckle_size, 4 + 2 + 8 + 4 + 2 + 4 + 4),
+        }
+        h.stereo_depth(0, B, pair=0, stream=s)
+        raw = torch.from_numpy(np.stack([h.stereo_depth_read(f)[1] for f in range(B)]).view(np.int16)).cuda()   # unfiltered disp32
+        flt = {"median_window": args.median, "speckle_size": args.speckle_size, "speckle_range": args.speckle_range,
+               "box_us_per_frame": round(us_batch / B, 2)}
+        for name, (m, size, bpp) in settings.items():
+            h.stereo_depth_filter(median=m, speckle_size=size, speckle_range=args.speckle_range)
+            timed(run, 2)
+            with_trials = [timed(run, args.reps) for _ in range(3)]
+            depth_f = h.stereo_depth_read(B - 1)[0]
+            alone = lambda: h.stereo_depth_filter_apply(raw.data_ptr(), W, H, rect.fx * rect.baseline, B, stream=s)   # noqa: E731
+            timed(alone, 2)
+            alone_trials = [timed(alone, args.reps) for _ in range(3)]
+            us = (min(with_trials) - us_batch) / B
+            flt[name] = {
+                "matcher_and_filter_us_per_batch_trials": [round(t, 1) for t in with_trials],
+                "filter_us_per_frame": round(us, 2),                       # beside the matcher's own trials above
+                "filter_apply_us_per_batch_trials": [round(t, 1) for t in alone_trials],
+                "filter_apply_us_per_frame": round(min(alone_trials) / B, 2),   # includes the clamping copy (4 B / px more)
+                "bytes_per_frame": bpp * px,
+                "achieved_GBps": round(bpp * px / max(us, 1e-3) / 1e3, 2),
+                "over_box_matcher": round(us * B / us_batch, 3),
+                "valid_fraction_last_frame": round(float((depth_f > 0).mean()), 4),
+            }
+        h.stereo_depth_filter(enable=False)
+
     h.begin_batch(dev.data_ptr(), B)
     h.run_kernel("rectify_pyramid", s)
     timed(lambda: h.run_kernel("detect", s), 2)
@@ -133,6 +181,8 @@ def main() -> None:
     }
     if sgm is not None:
         out["sgm"] = sgm
+    if flt is not None:
+        out["filter"] = flt
     line = json.dumps(out)
     print(line)
     if args.out:
