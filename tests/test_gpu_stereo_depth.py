@@ -84,8 +84,11 @@ def _check_images(h, frames, fxb, n_disp, uniqueness=10, lr_tol=1, want_valid=Tr
 
 
 # (W, H, D, baseline): below one step and band-ragged; one step with a ragged band and D off 32;
-# two steps (320 = 252 + 68) at the handle's size; the default baseline; D > W / 2
-SHAPES = [(72, 40, 24, 0.3), (200, 136, 40, 0.3), (320, 240, 64, 0.3), (320, 240, 32, 0.075), (96, 64, 64, 0.3)]
+# two steps (320 = 252 + 68) at the handle's size; the default baseline; D > W / 2; then widths and
+# heights that are no multiple of 8 (or of 2): odd both ways, one column past the 252-column step,
+# and a wide strip of two bands and one row
+SHAPES = [(72, 40, 24, 0.3), (200, 136, 40, 0.3), (320, 240, 64, 0.3), (320, 240, 32, 0.075), (96, 64, 64, 0.3),
+          (75, 43, 24, 0.3), (101, 67, 40, 0.3), (253, 41, 72, 0.3), (257, 17, 24, 0.3)]
 
 
 @pytest.mark.parametrize("width,height,n_disp,baseline", SHAPES)

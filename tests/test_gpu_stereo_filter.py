@@ -138,6 +138,26 @@ def test_images_bit_exact(handle, width, height, n_disp, m):
     _assert_same(got[0], (BOX.depth_from_disp32(out, fxb), out), f"{width}x{height} m {m}")
 
 
+# widths and heights off every multiple of 8 (the filter's hand-made planes are 75 x 43; here the
+# matcher feeds it at such shapes): odd both ways, one column past the matcher's 252-column step, a
+# strip of 17 rows.  SIZE_ODD: components of up to 20 pixels, so that the small images lose some.
+ODD_SHAPES = [(75, 43, 24), (101, 67, 40), (253, 41, 72), (257, 17, 24)]
+SIZE_ODD = 20
+
+
+@pytest.mark.parametrize("width,height,n_disp", ODD_SHAPES)
+def test_images_odd_shapes_median_and_speckle(handle, width, height, n_disp):
+    frames, fxb = _rendered(width, height)
+    raw = _matched(width, height, 0, n_disp)
+    med = FLT.median(raw, 5)
+    out = FLT.speckle(med, SIZE_ODD, RANGE)
+    changed, removed = int((med != raw).sum()), int(((out == 0) & (med != 0)).sum())
+    print(f"{width}x{height}: the median changes {changed} pixels, the speckle step removes {removed}")
+    assert changed >= 100 and removed >= 10        # a kernel that does nothing cannot pass
+    got = _run_images(handle, frames[:1], fxb, n_disp, flt=dict(median=5, speckle_size=SIZE_ODD, speckle_range=RANGE))
+    _assert_same(got[0], (BOX.depth_from_disp32(out, fxb), out), f"{width}x{height}")
+
+
 def test_images_two_frames(handle):
     frames, fxb = _rendered(72, 40)
     got = _run_images(handle, frames, fxb, 24, flt=dict(median=5, speckle_size=SIZE, speckle_range=RANGE))

@@ -93,7 +93,10 @@ def _assert_same(got, want, what=""):
 
 # (W, H, D): below one step, ragged band, D < 64; D off 32; D > W / 2 and D > 64 off a multiple of
 # 64; two steps of the volume at the handle's size; the largest D over three bands.  Baseline 0.3.
-SHAPES = [(72, 40, 24), (200, 136, 40), (96, 64, 72), (320, 240, 64), (320, 24, 256)]
+# Then widths and heights off every multiple of 8: odd both ways, one column past the 252-column
+# step of the box matcher, and a wide strip of 17 rows.
+SHAPES = [(72, 40, 24), (200, 136, 40), (96, 64, 72), (320, 240, 64), (320, 24, 256),
+          (75, 43, 24), (101, 67, 40), (253, 41, 72), (257, 17, 24)]
 
 
 @pytest.mark.parametrize("width,height,n_disp", SHAPES)
