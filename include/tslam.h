@@ -130,7 +130,8 @@ enum tslam_buffer {
     TSLAM_BUF_DISP = 6,      /* f64 [ring][pairs][K]             refined level-0 disparity/NaN */
     TSLAM_BUF_TEMPORAL = 7,  /* i32 [ring][pairs][K]             left(t-1) index or -1        */
     TSLAM_BUF_TEMPORAL_UV = 8, /* f64 [batch][pairs][K][2]       refined (u, v) at t / NaN    */
-    TSLAM_BUF_CORR = 9,      /* f64 [batch][pairs][K][8]         X Y Z du dv bx by bz         */
+    TSLAM_BUF_CORR = 9,      /* f64 [batch][pairs][K][8]         X Y Z du dv bx by bz (a foreign pair's
+                                rows on a sharded rank: columns 0-4 only, see tslam_unpack_pairs) */
     TSLAM_BUF_POSE = 10,     /* f64 [batch][pairs][68]           T_rel[16] T_abs[16] cov[36]  */
     TSLAM_BUF_STATS = 11,    /* i32 [batch][pairs][8]            status n_corr n_inl best ... */
     TSLAM_BUF_QBEST = 12,    /* u32 [batch][pairs][2][K]         (dist<<16 | idx) stereo, temporal */
@@ -413,7 +414,9 @@ int tslam_set_shard(tslam_handle* h, int cam_lo, int cam_hi, int rank, int world
  * X, Y, Z, cx - u, cy - v; rows past stats[1] are not copied). */
 int tslam_pair_block_bytes(tslam_handle* h, int64_t* bytes);
 /* Pair blocks of batch frames f0 .. f0+n_frames-1 x pairs [pair_lo, pair_hi) (frame-major) to / from
- * device memory, inside a batch (pack after POSE, unpack before KERNEL_RIG). */
+ * device memory, inside a batch (pack after POSE, unpack before KERNEL_RIG).  A block carries
+ * correspondence columns 0-4 only: after tslam_unpack_pairs, columns 5-7 (bx by bz) of those rows
+ * of TSLAM_BUF_CORR are stale on the receiving rank. */
 int tslam_pack_pairs(tslam_handle* h, int f0, int n_frames, int pair_lo, int pair_hi, void* dst, void* stream);
 int tslam_unpack_pairs(tslam_handle* h, int f0, int n_frames, int pair_lo, int pair_hi, const void* src, void* stream);
 /* Bytes of one stream block (per frame and camera) and of one pose record (per frame). */

@@ -1,11 +1,12 @@
 // host_check.cpp — the library's host-side C++ under AddressSanitizer + UndefinedBehaviorSanitizer
 // (`make -C thor-slam_amd/csrc sanitize`; tests/test_sanitizers.py).  Linked with the host sources
-// themselves (tslam_calib.cpp, tslam_imu.cpp, tslam_ranges.h) — not with libtslam_hip.so — so the
+// themselves (tslam_calib.cpp, tslam_imu.cpp, tslam_ranges.h, tslam_xplan.h) — not with libtslam_hip.so — so the
 // sanitizer runtime comes first in this executable and nothing has to be preloaded.
 //
 //   host_check maps  calib.txt out.bin   tslam_rig_pairs + tslam_rectify_pair (rig_from_calib.c's format)
 //   host_check imu   script.bin out.bin  the tslam_imu_* filter over a scripted sequence
 //   host_check ranges                    the sharded frame-range arithmetic, exhaustively
+//   host_check schedule                  the sharded exchange plan: every rank's operations, simulated
 // Exit status 0 on success; a sanitizer report aborts (-fno-sanitize-recover=all).
 #include <algorithm>
 #include <cmath>
@@ -18,6 +19,7 @@
 
 #include "../../include/tslam.h"
 #include "../../thor-slam_amd/csrc/tslam_ranges.h"
+#include "../../thor-slam_amd/csrc/tslam_xplan.h"
 
 // tslam_api.cpp's error setter (the host sources report through it)
 static std::string g_err;
@@ -203,10 +205,161 @@ static int cmd_ranges() {
     return 0;
 }
 
+// ---- schedule: all ranks' exchange plans (tslam_xplan.h), simulated -------------------------------
+// What rank src's exchange `kind` must deliver to rank dst, from the rule itself (not the plan's
+// size helpers): rank q's back end reads frames lo - 1 .. hi - 1 of the other cameras (raw image
+// + stream block each), lo .. hi of its frame range, or under the pair split of its pair's half, and
+// of the partner camera only; a rig range takes one pair block per frame and foreign pair (RGB-D:
+// camera; pair split: the pairs of the same half's ranks); rank 0 gathers every range's state of
+// all pairs and every frame's state of the sender's left (even) cameras; every rank gets every
+// rank's pose records, padded to the longest range.
+static size_t sched_expect(const XGeom& g, int kind, int src, int dst) {
+    const int N = g.world, n = g.n;
+    int lo, hi, left = 0;
+    if (kind == X_POSE) return (size_t)((n + N - 1) / N) * g.rec;
+    if (src == dst) return 0;
+    switch (kind) {
+    case X_RAW:
+    case X_FEAT:
+        if (g.rgbd) {
+            peer_range(dst, n, N, &lo, &hi);
+            return kind == X_RAW ? 0 : (size_t)(hi - lo) * g.S * g.pblk;
+        }
+        if (g.pairs && src != (dst ^ 1)) return 0;
+        if (g.pairs) peer_range(dst & 1, n, 2, &lo, &hi);
+        else peer_range(dst, n, N, &lo, &hi);
+        return hi > lo ? (size_t)(hi - lo + 1) * g.S * (kind == X_RAW ? g.img : g.sblk) : 0;
+    case X_PAIRB:
+        if (!g.pairs || ((src ^ dst) & 1)) return 0;
+        peer_range(rig_slot(dst, N, 1), n, N, &lo, &hi);
+        return (size_t)(hi - lo) * g.pblk;
+    default:   // X_STATE
+        if (!g.gather || dst != 0) return 0;
+        peer_range(src, n, N, &lo, &hi);
+        for (int c = src * g.S; c < (src + 1) * g.S; ++c) left += c % 2 == 0;
+        return (size_t)(hi - lo) * g.P * g.st_range + (size_t)n * left * g.st_cam;
+    }
+}
+
+namespace {
+constexpr int XW = 16;   // the largest world of the grid
+struct Fifo {            // one direction of one (rank, peer, communicator): at most two operations
+    int n = 0;
+    XOp op[2];
+};
+Fifo g_snd[XW][XW][2], g_rcv[XW][XW][2];   // [rank][peer][communicator]
+}  // namespace
+
+#define SCHED_FAIL(what)                                                                                          \
+    do {                                                                                                          \
+        fprintf(stderr, "schedule: %s (kind %d, src %d, dst %d; world %d S %d max_batch %d n %d rgbd %d pairs %d gather %d)\n", \
+                what, kind, src, dst, g.world, g.S, g.B, g.n, g.rgbd, g.pairs, g.gather);                         \
+        return 1;                                                                                                 \
+    } while (0)
+
+// One exchange of one batch: pairing, placement, sources, coverage and topology over all ranks.
+static int sched_case(const XGeom& g, int kind) {
+    const int N = g.world;
+    const size_t frame = (size_t)g.S * g.img;
+    int src = -1, dst = -1, overflow = 0;
+    for (int r = 0; r < N; ++r)
+        for (int q = 0; q < N; ++q)
+            for (int c = 0; c < 2; ++c) g_snd[r][q][c].n = g_rcv[r][q][c].n = 0;
+    auto push = [&](int r, const XOp& o) {
+        Fifo& f = (o.send ? g_snd : g_rcv)[r][o.peer][o.comm];
+        if (o.peer < 0 || o.peer >= N || f.n == 2) overflow = 1;
+        else f.op[f.n++] = o;
+    };
+    for (int r = 0; r < N; ++r) {
+        if (kind != X_POSE) {   // the ranks' own point-to-point lists
+            xp_ops(g, kind, r, [&](const XOp& o) { push(r, o); });
+            continue;
+        }
+        for (int q = 0; q < N; ++q)   // the all-gather as copies; a receive per send by construction
+            xp_sends(g, kind, r, q, [&](const XOp& o) { push(r, o), push(q, XOp{false, r, o.comm, XB_RECV, o.dst_off, o.bytes, 0}); });
+    }
+    if (overflow) SCHED_FAIL("more than two operations per peer and direction, or a peer outside the world");
+    const bool on_p = kind >= X_PAIRB;   // PAIRB, STATE, POSE: the back stream's communicator
+    for (dst = 0; dst < N; ++dst) {
+        size_t prev_end = 0;   // placement: the slots of the sources, in rank order
+        for (src = 0; src < N; ++src) {
+            const Fifo &s = g_snd[src][dst][on_p], &r = g_rcv[dst][src][on_p];
+            if (g_snd[src][dst][!on_p].n || g_rcv[dst][src][!on_p].n) SCHED_FAIL("operation on the other communicator");
+            // pairing: src's sends to dst are dst's receives from src, in count, order, bytes (and place)
+            if (s.n != r.n) SCHED_FAIL("sends and receives differ in count");
+            const size_t want = sched_expect(g, kind, src, dst);
+            if ((s.n != 0) != (want != 0)) SCHED_FAIL(want ? "nothing sent where data is due" : "topology: a send where none is due");
+            if (s.n == 0) continue;
+            if (src == dst && kind != X_POSE) SCHED_FAIL("topology: a rank sends to itself");
+            const size_t slot = xp_slot_off(g, kind, XB_RECV, src), cap = kind == X_POSE ? want : xp_slot(g, kind);
+            if (slot < prev_end) SCHED_FAIL("placement: the slots of two sources overlap");
+            if (slot + cap > xp_buf_bytes(g, kind, XB_RECV, dst)) SCHED_FAIL("placement: slot outside the receive buffer");
+            prev_end = slot + cap;
+            size_t at = slot;   // coverage: the pieces tile the slot from offset 0
+            int lo, hi;         // RAW sources: frames lo - 1 .. hi - 1, frame -1 from prev_raw
+            if (g.pairs) peer_range(dst & 1, g.n, 2, &lo, &hi);
+            else peer_range(dst, g.n, N, &lo, &hi);
+            int64_t f = lo - 1;
+            for (int j = 0; j < s.n; ++j) {
+                const XOp &a = s.op[j], &b = r.op[j];
+                if (a.bytes != b.bytes || a.bytes == 0) SCHED_FAIL("pairing: bytes differ (or an empty operation)");
+                if (a.dst_off != b.off || b.buf != XB_RECV) SCHED_FAIL("pairing: the receive is not where the send lands");
+                if (b.off != at) SCHED_FAIL("coverage: gap or overlap in the slot");
+                at += b.bytes;
+                if (at > slot + cap) SCHED_FAIL("placement: receive outside the slot of its source");
+                if (kind == X_RAW) {   // sources: straight from the input and prev_raw
+                    if (a.bytes % frame) SCHED_FAIL("sources: not whole frames");
+                    if (f < 0 ? (a.buf != XB_PREV || a.off != 0 || a.bytes != frame)
+                              : (a.buf != XB_INPUT || a.off != (size_t)f * frame || a.off + a.bytes > (size_t)g.n * frame))
+                        SCHED_FAIL("sources: not the frames the peer reads");
+                    f += (int64_t)(a.bytes / frame);
+                } else {               // sources: the send slot of the destination
+                    const size_t so = xp_slot_off(g, kind, XB_SEND, dst);
+                    if (a.buf != XB_SEND || a.off != so || so + xp_slot(g, kind) > xp_buf_bytes(g, kind, XB_SEND, src) ||
+                        a.bytes > xp_slot(g, kind))
+                        SCHED_FAIL("sources: outside the send slot");
+                }
+            }
+            if (at - slot != want) SCHED_FAIL("coverage: not the expected byte count");
+            if (kind == X_RAW && f != hi) SCHED_FAIL("sources: frames missing");
+            // topology, stated on its own
+            if (kind == X_STATE && dst != 0) SCHED_FAIL("topology: state to a rank other than 0");
+            if (g.pairs && kind <= X_FEAT && dst != (src ^ 1)) SCHED_FAIL("topology: pair split stereo data past the partner");
+            if (kind == X_PAIRB && ((src ^ dst) & 1)) SCHED_FAIL("topology: pair blocks across the halves");
+            if ((kind == X_PAIRB && !g.pairs) || (kind == X_STATE && !g.gather) || (g.rgbd && kind != X_FEAT && kind != X_POSE))
+                SCHED_FAIL("topology: a kind the layout does not use");
+        }
+    }
+    return 0;
+}
+
+// world x max_batch x every n x cameras per rank x layout (stereo frame ranges with and without the
+// state gather, the stereo pair split, camera-sharded RGB-D); odd unit sizes, so that a wrong
+// factor shows in the byte counts.
+static int cmd_schedule() {
+    long cases = 0;
+    for (int world : {1, 2, 3, 4, 6, 8, 16})
+        for (int B = world; B <= 64; B = B < 16 ? B + 1 : B + 1 + B / 8)   // every max_batch to 16, then 19, 22 .. 56, 64
+            for (int n = 1; n <= B; ++n)
+                for (int S = 1; S <= 2; ++S)
+                    for (int layout = 0; layout < 4; ++layout) {   // frames, frames + gather, pairs, RGB-D
+                        const bool rgbd = layout == 3, pairs = layout == 2, gather = layout == 1;
+                        if (!rgbd && (world * S) % 2) continue;                      // a stereo rig has whole pairs
+                        if ((gather && world < 2) || (pairs && (world % 2 || S != 1))) continue;
+                        const XGeom g{world, S, rgbd ? world * S : world * S / 2, B, n, 1003, 37, 11, 7, 5, 3, rgbd, pairs, gather};
+                        for (int kind = 0; kind < X_KINDS; ++kind)
+                            if (sched_case(g, kind)) return 1;
+                        ++cases;
+                    }
+    printf("schedule: %ld (world, max_batch, n, cameras, layout) cases\n", cases);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc >= 4 && !strcmp(argv[1], "maps")) return cmd_maps(argv[2], argv[3]);
     if (argc >= 4 && !strcmp(argv[1], "imu")) return cmd_imu(argv[2], argv[3]);
     if (argc >= 2 && !strcmp(argv[1], "ranges")) return cmd_ranges();
-    fprintf(stderr, "usage: host_check maps calib.txt out.bin | imu script.bin out.bin | ranges\n");
+    if (argc >= 2 && !strcmp(argv[1], "schedule")) return cmd_schedule();
+    fprintf(stderr, "usage: host_check maps calib.txt out.bin | imu script.bin out.bin | ranges | schedule\n");
     return 2;
 }

@@ -1,6 +1,6 @@
 """SURVEY.md §5 robustness: the library's host C++ — calibration / rectification tables
-(tslam_calib.cpp), the IMU filter (tslam_imu.cpp) and the sharded frame-range arithmetic
-(tslam_ranges.h) — built with AddressSanitizer + UndefinedBehaviorSanitizer (`make sanitize`:
+(tslam_calib.cpp), the IMU filter (tslam_imu.cpp), the sharded frame-range arithmetic
+(tslam_ranges.h) and the sharded exchange plan (tslam_xplan.h) — built with AddressSanitizer + UndefinedBehaviorSanitizer (`make sanitize`:
 tests/c/host_check.cpp links the host sources into an executable of its own, any report aborts)
 and run on the inputs the product tests use; its outputs must equal the ctypes library's and the
 Python product's byte for byte.  CPU only."""
@@ -54,10 +54,21 @@ def _run(exe, *args):
 
 
 def test_sanitizer_target_ranges(exe):
-    """`make sanitize` (the Makefile target) builds the executable and runs the exhaustive range check."""
+    """`make sanitize` (the Makefile target) builds the executable and runs the exhaustive range
+    check, then the exchange schedule check; each prints its case count."""
     out = subprocess.run(["make", "-s", "-C", str(CSRC), "sanitize"], capture_output=True, text=True)
     assert out.returncode == 0, out.stderr[-3000:]
     assert "cases" in out.stdout
+    assert "ranges: " in out.stdout and "schedule: " in out.stdout
+
+
+def test_sanitized_exchange_schedule(exe):
+    """The exchange plan of the sharded-rig driver, all ranks simulated (world 1..16, every batch
+    size, every layout): each rank's sends are its peer's receives in count, order and bytes on the
+    same communicator, every piece lies in its source's slot and the pieces tile it to the byte
+    count the back end's frame rule gives, and no layout sends where it has no business."""
+    out = _run(exe, "schedule")
+    assert out.stdout.startswith("schedule: ") and int(out.stdout.split()[1]) > 10000
 
 
 def test_sanitized_rectification_tables_match_calib(exe, tmp_path):

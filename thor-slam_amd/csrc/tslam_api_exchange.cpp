@@ -212,6 +212,8 @@ int tslam_internal_info(tslam_handle* h, tslam_handle_info* o) {
     o->stream_block = stream_block_bytes(h->g);
     o->pose_record = pose_record_bytes(h->P);
     o->pair_block = pair_block_bytes(h->g);
+    o->state_range = state_range_block_bytes(h->g);
+    o->state_camera = state_camera_block_bytes(h->g);
     o->cam_lo = h->sh_cam_lo;
     o->cam_hi = h->sh_cam_hi;
     o->rank = h->sh_rank;
@@ -229,13 +231,6 @@ int tslam_internal_attach_driver(tslam_handle* h, tslam_shard_driver* d, bool ow
 }
 
 tslam_shard_driver* tslam_internal_driver(tslam_handle* h) { return h ? h->drv : nullptr; }
-
-int64_t tslam_internal_state_bytes(tslam_handle* h, int n, int rank, int cam_lo, int cam_hi) {
-    int lo, hi;
-    peer_range(rank, n, h->sh_world, &lo, &hi);
-    const int left0 = (cam_lo + 1) & ~1, nleft = cam_hi > left0 ? (cam_hi - left0 + 1) / 2 : 0;
-    return (int64_t)(hi - lo) * h->P * state_range_block_bytes(h->g) + (int64_t)n * nleft * state_camera_block_bytes(h->g);
-}
 
 int tslam_internal_state_blocks(tslam_handle* h, int pack, int rank, int cam_lo, int cam_hi, void* buf, void* stream) {
     if (!h || !buf) return fail(TSLAM_EINVAL, "bad argument");
@@ -269,14 +264,20 @@ static int check_peers(tslam_handle* h) {
         return fail(TSLAM_EINVAL, "peer layout needs cameras [rank*S, (rank+1)*S)");
     return TSLAM_OK;
 }
+// the exchange plan's geometry of the current batch (tslam_xplan.h: the frame-range slot layout)
+static XGeom peers_geom(tslam_handle* h) {
+    tslam_handle_info in{};
+    (void)tslam_internal_info(h, &in);
+    return tslam_xgeom(in, h->sh_world, h->cur_n, false, false);
+}
 
 int tslam_pack_streams_peers(tslam_handle* h, void* dst, void* stream) {
     int rc = check_peers(h);
     if (rc != TSLAM_OK) return rc;
     if (!dst) return fail(TSLAM_EINVAL, "null buffer");
     HIPCHK(hipSetDevice(h->device));
-    const int N = h->sh_world, S = h->sh_cam_hi - h->sh_cam_lo;
-    launch_stream_blocks_peers(make_ctx(h), true, h->cur_g0, h->cur_n, N, peer_cap(h->B, N), h->sh_rank, S, (uint8_t*)dst,
+    const XGeom g = peers_geom(h);
+    launch_stream_blocks_peers(make_ctx(h), true, h->cur_g0, g.n, g.world, xp_slot_frames(g), h->sh_rank, g.S, (uint8_t*)dst,
                                (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return TSLAM_OK;
@@ -287,9 +288,9 @@ int tslam_stage_raw_peers(tslam_handle* h, const uint8_t* prev_raw, void* dst, v
     if (rc != TSLAM_OK) return rc;
     if (!prev_raw || !dst) return fail(TSLAM_EINVAL, "null buffer");
     HIPCHK(hipSetDevice(h->device));
-    const int N = h->sh_world, S = h->sh_cam_hi - h->sh_cam_lo;
-    launch_stage_raw_peers(h->cur_images, prev_raw, (uint8_t*)dst, h->cur_n, N, peer_cap(h->B, N), h->sh_rank, S,
-                           (int64_t)h->W * h->H, (hipStream_t)stream);
+    const XGeom g = peers_geom(h);
+    launch_stage_raw_peers(h->cur_images, prev_raw, (uint8_t*)dst, g.n, g.world, xp_slot_frames(g), h->sh_rank, g.S,
+                           (int64_t)g.img, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return TSLAM_OK;
 }
@@ -299,24 +300,23 @@ int tslam_import_peers(tslam_handle* h, const uint8_t* raw, const void* streams,
     if (rc != TSLAM_OK) return rc;
     if (!raw || !streams) return fail(TSLAM_EINVAL, "null buffer");
     HIPCHK(hipSetDevice(h->device));
-    const int N = h->sh_world, S = h->sh_cam_hi - h->sh_cam_lo, cap = peer_cap(h->B, N);
-    const int nr = peer_frames(h->sh_rank, h->cur_n, N);
+    const XGeom g = peers_geom(h);
+    int lo;
+    const int nr = xp_back_frames(g, h->sh_rank, &lo);
     if (nr == 0) return TSLAM_OK;   // an empty frame range: this rank's back end has nothing to do
-    int lo, hi;
-    shard_range(h, h->cur_n, &lo, &hi);
     const int64_t first = h->cur_g0 + lo - 1;
     const int skip = first < 0 ? 1 : 0;   // frame -1 (before the sequence start) is not imported
     BatchCtx c = make_ctx(h);
     c.images = raw;
     c.g0 = first + skip;
     c.n = nr - skip;
-    c.peer_S = S;
+    c.peer_S = g.S;
     c.peer_me = h->sh_rank;
-    c.peer_nbuf = cap;
+    c.peer_nbuf = xp_slot_frames(g);
     c.peer_skip = skip;
     if (c.n > 0) launch_rectify_pyramid(c, (hipStream_t)stream);
-    launch_stream_blocks_peers(make_ctx(h), false, h->cur_g0, h->cur_n, N, cap, h->sh_rank, S, (uint8_t*)streams,
-                               (hipStream_t)stream);
+    launch_stream_blocks_peers(make_ctx(h), false, h->cur_g0, g.n, g.world, xp_slot_frames(g), h->sh_rank, g.S,
+                               (uint8_t*)streams, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return TSLAM_OK;
 }

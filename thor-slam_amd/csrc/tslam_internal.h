@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/tslam.h"
+#include "tslam_xplan.h"
 
 struct tslam_shard_driver;   // tslam_shard.cpp
 
@@ -20,9 +21,15 @@ struct tslam_handle_info {
     int device, W, H, P, C, B, rgbd, rig, ba;
     int64_t frames_done;
     int64_t stream_block, pose_record, pair_block;   // exchange unit sizes (bytes)
+    int64_t state_range, state_camera;               // state gather: per (frame, pair) of a range, per (frame, left camera)
     int cam_lo, cam_hi, rank, world;                 // tslam_set_shard
 };
 TSLAM_INTERNAL int tslam_internal_info(tslam_handle* h, tslam_handle_info* out);
+// the exchange plan's geometry (tslam_xplan.h) of the handle's rig sharded over `world` ranks
+static inline XGeom tslam_xgeom(const tslam_handle_info& in, int world, int n, bool pairs, bool gather) {
+    return XGeom{world, in.C / world, in.P, in.B, n, (size_t)in.W * in.H, (size_t)in.stream_block, (size_t)in.pair_block,
+                 (size_t)in.pose_record, (size_t)in.state_range, (size_t)in.state_camera, in.rgbd != 0, pairs, gather};
+}
 
 // `owned`: the handle destroys the driver with itself (tslam_comm_init); a group's driver is owned
 // by the group (tslam_group_destroy detaches it first).  NULL detaches.
@@ -30,10 +37,9 @@ TSLAM_INTERNAL int tslam_internal_attach_driver(tslam_handle* h, tslam_shard_dri
 TSLAM_INTERNAL tslam_shard_driver* tslam_internal_driver(tslam_handle* h);
 TSLAM_INTERNAL void tslam_internal_driver_destroy(tslam_shard_driver* d);
 
-// State gather of a sharded stereo rig (k_exchange.hip, state blocks): bytes of sender `rank`'s
-// payload for an n-frame batch; pack (on the sender, its own rank / cameras) or unpack (on rank 0,
-// the sender's rank and camera range) inside a batch, after the back end of the sender's range.
-TSLAM_INTERNAL int64_t tslam_internal_state_bytes(tslam_handle* h, int n, int rank, int cam_lo, int cam_hi);
+// State gather of a sharded stereo rig (k_exchange.hip, state blocks; xp_state_bytes each): pack
+// (on the sender, its own rank / cameras) or unpack (on rank 0, the sender's rank and camera
+// range) inside a batch, after the back end of the sender's range.
 TSLAM_INTERNAL int tslam_internal_state_blocks(tslam_handle* h, int pack, int rank, int cam_lo, int cam_hi, void* buf,
                                                void* stream);
 // the current batch's poses / stats into the handle's pinned result slots (tslam_poll_batch)

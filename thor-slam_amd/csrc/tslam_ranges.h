@@ -5,7 +5,8 @@
 // Rank q's back end owns batch frames [q n / world, (q + 1) n / world) of an n-frame batch (any n
 // in [1, max_batch]: ranges may differ by one frame or be empty) and reads the other cameras of
 // frames lo - 1 .. hi - 1 (none for an empty range).  Exchange slots are sized for a full batch:
-// peer_cap frames per peer; the pose all-gather pads every range to peer_records records.
+// peer_cap frames per peer; the pose all-gather pads every range to peer_records records.  What
+// the ranks exchange over these ranges — slot layout and schedule — is tslam_xplan.h.
 #pragma once
 
 #include <stdint.h>

@@ -20,9 +20,10 @@
 // collectives that read them are.  Nothing here synchronises the host.
 //
 // Any batch of 1 .. max_batch frames: rank q's back end owns frames [q n / N, (q + 1) n / N) (ranges
-// may differ by a frame or be empty), exchange slots are sized for a full batch (peer_cap frames),
-// the pose all-gather pads every range to peer_records(n, N) records.  Raw images go straight from
-// the caller's input (and the previous batch's last frame) to the peers: no staging copy.
+// may differ by a frame or be empty).  Who sends what to whom, and where it lands, is the exchange
+// plan (tslam_xplan.h): the slot layout of every buffer and each rank's ordered operations per
+// exchange; this file allocates, packs, issues and unpacks by it.  Raw images go straight from the
+// caller's input (and the previous batch's last frame) to the peers: no staging copy.
 //
 // Pair split (TSLAM_SHARD_PAIRS, one camera per rank): rank r's back end solves pair r / 2 over
 // half r & 1 of the batch, so the raw images and stream blocks go to the partner (r ^ 1) only —
@@ -40,8 +41,9 @@
 // the pose all-gather of batch s, on the back stream, never shares a communicator with batch s+1's
 // exchange on the exchange stream), created per process (tslam_comm_init: one local rank) or for
 // all devices of one process (tslam_group_create: ncclCommInitAll); or COPY (device-to-device
-// copies pushed on the sender's stream: a group of ranks in one process, also several on one device
-// — the same packing and ordering as RCCL, used to test world > 1 on one GPU).
+// copies pushed on the sender's stream: a group of ranks in one process, also several on one device,
+// used to test world > 1 on one GPU).  Both issue the plan's operations: RCCL a rank's sends and
+// receives in one group, COPY every rank's sends as copies to the plan's destination offsets.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -88,15 +90,9 @@ struct Rank {
     hipEvent_t consumed[2] = {nullptr, nullptr};   // this parity's receive buffers were read
     bool consumed_armed[2] = {false, false};
     bool done_armed = false;
-    uint8_t* raw_recv[2] = {nullptr, nullptr};
-    uint8_t* feat_send[2] = {nullptr, nullptr};    // stream blocks (stereo) or pair blocks (RGB-D)
-    uint8_t* feat_recv[2] = {nullptr, nullptr};
-    uint8_t* pose_send[2] = {nullptr, nullptr};
-    uint8_t* pose_recv[2] = {nullptr, nullptr};
-    uint8_t* state_buf[2] = {nullptr, nullptr};    // gather: the payload (sender) / all payloads (rank 0)
-    uint8_t* pb_send[2] = {nullptr, nullptr};      // pair split: pair blocks per rig-range owner
-    uint8_t* pb_recv[2] = {nullptr, nullptr};
-    uint8_t* prev_raw = nullptr;   // the previous batch's last frame of this rank's cameras
+    uint8_t* send[X_KINDS][2] = {};   // the exchange buffers by kind and batch parity (tslam_xplan.h)
+    uint8_t* recv[X_KINDS][2] = {};
+    uint8_t* prev_raw = nullptr;      // the previous batch's last frame of this rank's cameras
     std::vector<void*> allocs;
     // profiling
     std::vector<hipEvent_t> ev_pool;
@@ -105,26 +101,23 @@ struct Rank {
     double seg_us[TSLAM_SEG_COUNT] = {};
     int64_t timed_batches = 0;
 };
-
-enum Which { RAW = 0, FEAT = 1, POSE = 2, STATE = 3, PAIRB = 4 };
 }  // namespace
 
 struct tslam_shard_driver {
-    int world = 1, transport = TSLAM_TRANSPORT_RCCL;
-    bool rgbd = false, rig = false, ba = false;
+    int transport = TSLAM_TRANSPORT_RCCL;
+    XGeom g{};                           // the exchange plan's geometry: the rig, the options, this batch's n
+    bool rig = false, ba = false;
     int flags = 0;                       // TSLAM_SHARD_* options
-    int S = 0, B = 0, cap = 0;           // cameras per rank, max_batch, frames per peer slot
-    int P = 0;                           // stereo pairs (RGB-D: cameras)
-    int n = 0, maxr = 0;                 // this batch: frames, pose records per rank in the all-gather
-    size_t img = 0, rec = 0, sblk = 0, pblk = 0;   // bytes: image, pose record, stream block, pair block
-    size_t state_cap = 0;                // bytes of one sender's state payload slot (full batch)
-    bool pb_ready = false;               // pair split: pair-block buffers allocated
+    bool ready[X_KINDS] = {};            // the kind's buffers are allocated
     int64_t batches = 0;
     std::vector<Rank> ranks;   // local ranks: all of a group, one after tslam_comm_init
-    bool gather() const { return world > 1 && !rgbd && (ba || (flags & TSLAM_SHARD_GATHER)); }
-    // TSLAM_SHARD_PAIRS: rank r's back end solves pair r / 2 over half r & 1 of the batch; the
-    // stereo exchange goes to the partner (r ^ 1) only, the rig pose gathers pair blocks
-    bool pairs() const { return (flags & TSLAM_SHARD_PAIRS) != 0; }
+    // TSLAM_SHARD_GATHER is implied by local BA; TSLAM_SHARD_PAIRS: rank r's back end solves pair
+    // r / 2 over half r & 1 of the batch, the stereo exchange goes to the partner (r ^ 1) only
+    void set_flags(int f) {
+        flags = f;
+        g.gather = g.world > 1 && !g.rgbd && (ba || (f & TSLAM_SHARD_GATHER));
+        g.pairs = (f & TSLAM_SHARD_PAIRS) != 0;
+    }
 };
 
 // The rank's streams: its own three, or with TSLAM_SHARD_SERIAL one stream per device shared by
@@ -172,47 +165,30 @@ static int plan(tslam_shard_driver* d, tslam_handle* h, int world) {
     if (in.ba && in.rgbd) return tslam_internal_fail(TSLAM_EINVAL, "a camera-sharded RGB-D rig runs without local BA");
     if (in.C % world) return tslam_internal_fail(TSLAM_EINVAL, "the cameras must divide by world");
     if (world > in.B) return tslam_internal_fail(TSLAM_EINVAL, "world must be <= max_batch");
-    d->world = world;
-    d->rgbd = in.rgbd != 0;
     d->rig = in.rig != 0;
     d->ba = in.ba != 0;
-    d->S = in.C / world;
-    d->P = in.P;
-    d->B = in.B;
-    d->cap = peer_cap(in.B, world);
-    d->img = (size_t)in.W * in.H;
-    d->rec = (size_t)in.pose_record;
-    d->sblk = (size_t)in.stream_block;
-    d->pblk = (size_t)in.pair_block;
+    d->g = tslam_xgeom(in, world, 0, false, false);
+    d->set_flags(0);
     return TSLAM_OK;
 }
 
-// The frames rank q's stereo back end solves: its frame range, or under the pair split its pair's
-// half of the batch; it reads the other cameras of frames lo - 1 .. hi - 1 (none when empty).
-static void back_range(const tslam_shard_driver* d, int q, int* lo, int* hi) {
-    if (d->pairs()) peer_range(q & 1, d->n, 2, lo, hi);
-    else peer_range(q, d->n, d->world, lo, hi);
+// A rank's send and receive buffers of the exchanges in `kinds`, both parities, sized by the plan.
+static int setup_buffers(tslam_shard_driver* d, Rank& r, std::initializer_list<int> kinds) {
+    SHCHK(hipSetDevice(r.device));
+    for (int k = 0; k < 2; ++k)
+        for (int w : kinds) {
+            if (size_t b = xp_buf_bytes(d->g, w, XB_SEND, r.rank)) RC(alloc(r, &r.send[w][k], b));
+            if (size_t b = xp_buf_bytes(d->g, w, XB_RECV, r.rank)) RC(alloc(r, &r.recv[w][k], b));
+        }
+    SHCHK(hipDeviceSynchronize());   // the zeroing (null stream) lands before the rank's streams use them
+    return TSLAM_OK;
 }
-static int back_frames(const tslam_shard_driver* d, int q) {
-    int lo, hi;
-    back_range(d, q, &lo, &hi);
-    return hi > lo ? hi - lo + 1 : 0;
-}
-// does rank src send rank dst its raw images and stream blocks (pair split: the partner only)
-static bool stereo_peer(const tslam_shard_driver* d, int src, int dst) { return src != dst && (!d->pairs() || dst == (src ^ 1)); }
-
-// bytes rank `q`'s slot carries for this batch: raw images / stream blocks of the frames q's back end
-// reads (lo_q - 1 .. hi_q - 1) of S cameras; pair blocks (RGB-D) of q's range; slot capacities
-static size_t raw_bytes(const tslam_shard_driver* d, int q) { return (size_t)back_frames(d, q) * d->S * d->img; }
-static size_t feat_bytes(const tslam_shard_driver* d, int q) {
-    if (!d->rgbd) return (size_t)back_frames(d, q) * d->S * d->sblk;
-    int lo, hi;
-    peer_range(q, d->n, d->world, &lo, &hi);
-    return (size_t)(hi - lo) * d->S * d->pblk;
-}
-static size_t raw_cap(const tslam_shard_driver* d) { return (size_t)d->cap * d->S * d->img; }
-static size_t feat_cap(const tslam_shard_driver* d) {
-    return d->rgbd ? (size_t)(d->cap - 1) * d->S * d->pblk : (size_t)d->cap * d->S * d->sblk;
+// the buffers of an option (the state gather, the pair split's pair blocks), when first needed
+static int setup_option(tslam_shard_driver* d, int w, bool on) {
+    if (!on || d->ready[w]) return TSLAM_OK;
+    for (Rank& r : d->ranks) RC(setup_buffers(d, r, {w}));
+    d->ready[w] = true;
+    return TSLAM_OK;
 }
 
 static int setup_rank(tslam_shard_driver* d, Rank& r) {
@@ -227,64 +203,10 @@ static int setup_rank(tslam_shard_driver* d, Rank& r) {
     SHCHK(hipStreamCreateWithFlags(&r.bs, hipStreamNonBlocking));
     for (hipEvent_t* e : {&r.ev_in, &r.ev_front, &r.ev_x, &r.ev_push, &r.ev_done, &r.consumed[0], &r.consumed[1]})
         SHCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    const size_t N = d->world, maxr = (size_t)peer_records(d->B, d->world);
-    for (int k = 0; k < 2; ++k) {
-        if (!d->rgbd) RC(alloc(r, &r.raw_recv[k], N * raw_cap(d)));
-        RC(alloc(r, &r.feat_send[k], N * feat_cap(d)));
-        RC(alloc(r, &r.feat_recv[k], N * feat_cap(d)));
-        RC(alloc(r, &r.pose_send[k], maxr * d->rec));
-        RC(alloc(r, &r.pose_recv[k], N * maxr * d->rec));
-    }
-    if (!d->rgbd) RC(alloc(r, &r.prev_raw, (size_t)d->S * d->img));
-    SHCHK(hipDeviceSynchronize());   // the zeroing (null stream) lands before the rank's streams use them
+    RC(setup_buffers(d, r, {X_RAW, X_FEAT, X_POSE}));   // RGB-D: the plan gives RAW no bytes
+    if (!d->g.rgbd) RC(alloc(r, &r.prev_raw, (size_t)d->g.S * d->g.img));
+    SHCHK(hipDeviceSynchronize());
     return TSLAM_OK;
-}
-
-// The state-gather buffers (allocated when the gather is first needed): a sender's payload slot
-// holds its largest payload (a full batch); rank 0 keeps one slot per rank.
-static int setup_gather(tslam_shard_driver* d) {
-    if (!d->gather() || d->state_cap) return TSLAM_OK;
-    size_t cap = 0;
-    for (int q = 0; q < d->world; ++q)
-        cap = std::max(cap, (size_t)tslam_internal_state_bytes(d->ranks[0].h, d->B, q, q * d->S, (q + 1) * d->S));
-    d->state_cap = (cap + 255) / 256 * 256;
-    for (Rank& r : d->ranks) {
-        SHCHK(hipSetDevice(r.device));
-        for (int k = 0; k < 2; ++k) RC(alloc(r, &r.state_buf[k], (r.rank == 0 ? d->world : 1) * d->state_cap));
-        SHCHK(hipDeviceSynchronize());
-    }
-    return TSLAM_OK;
-}
-
-// The pair split's pair-block buffers (allocated when first needed): a slot per rank of the rig
-// range it owns (peer_records(max_batch, world) frames), sent to / received from the ranks of the
-// same half.  The stereo receive buffers need no change: world slots of peer_cap frames hold the
-// partner's half (max_batch / 2 + 1 frames) from offset 0.
-static int setup_pairs(tslam_shard_driver* d) {
-    if (!d->pairs() || d->pb_ready) return TSLAM_OK;
-    const size_t bytes = (size_t)d->world * peer_records(d->B, d->world) * d->pblk;
-    for (Rank& r : d->ranks) {
-        SHCHK(hipSetDevice(r.device));
-        for (int k = 0; k < 2; ++k) {
-            RC(alloc(r, &r.pb_send[k], bytes));
-            RC(alloc(r, &r.pb_recv[k], bytes));
-        }
-        SHCHK(hipDeviceSynchronize());
-    }
-    d->pb_ready = true;
-    return TSLAM_OK;
-}
-// pair split: rank q's rig range (rig pose + pose records), inside its pair's half
-static void rig_range(const tslam_shard_driver* d, int q, int* lo, int* hi) {
-    peer_range(rig_slot(q, d->world, 1), d->n, d->world, lo, hi);
-}
-static size_t pb_slot(const tslam_shard_driver* d) { return (size_t)peer_records(d->B, d->world) * d->pblk; }
-// does rank src send rank dst pair blocks (pair split: the other ranks of the same half)
-static bool pair_peer(const tslam_shard_driver* d, int src, int dst) { return src != dst && ((src ^ dst) & 1) == 0; }
-static size_t pb_bytes(const tslam_shard_driver* d, int dst) {   // one pair's blocks of dst's rig range
-    int lo, hi;
-    rig_range(d, dst, &lo, &hi);
-    return (size_t)(hi - lo) * d->pblk;
 }
 
 // ---- profiling (TSLAM_SHARD_PROFILE) ------------------------------------------------------------
@@ -318,154 +240,62 @@ static int run_timed(tslam_shard_driver* d, Rank& r, int seg, int stage, hipStre
     return span_end(d, r, s);
 }
 
-// ---- exchanges ----------------------------------------------------------------------------------
+// ---- exchanges (the plan: tslam_xplan.h) --------------------------------------------------------
 // The stream an exchange runs on (sender and receiver side): stereo raw images and stream blocks
 // on the exchange stream, pair blocks, state blocks and pose records on the back stream.
-static hipStream_t xstream(const tslam_shard_driver* d, const Rank& r, Which w) {
-    return (w == POSE || w == STATE || w == PAIRB || d->rgbd) ? BS(d, r) : XS(d, r);
+static hipStream_t xstream(const tslam_shard_driver* d, const Rank& r, int w) {
+    return (w >= X_PAIRB || d->g.rgbd) ? BS(d, r) : XS(d, r);
+}
+static uint8_t* buffer(const Rank& r, int w, int buf, int k, const uint8_t* images) {
+    return buf == XB_INPUT ? (uint8_t*)images : buf == XB_PREV ? r.prev_raw : buf == XB_SEND ? r.send[w][k] : r.recv[w][k];
 }
 
-// The pieces rank `src` sends rank `dst` for exchange w (at most two: a raw image slot of peer 0
-// starts with the previous batch's last frame), as (source pointer, destination offset, bytes).
-struct Piece {
-    const uint8_t* p;
-    size_t off, bytes;
-};
-static int pieces(const tslam_shard_driver* d, const Rank& src, int dst, Which w, int k, const uint8_t* images,
-                  Piece* out) {
-    if (w == RAW) {
-        const size_t frame = (size_t)d->S * d->img, total = raw_bytes(d, dst);
-        if (total == 0) return 0;
-        int lo, hi;
-        back_range(d, dst, &lo, &hi);
-        if (lo > 0) {   // frames lo-1 .. hi-1 are contiguous in the input
-            out[0] = {images + (size_t)(lo - 1) * frame, 0, total};
-            return 1;
-        }
-        out[0] = {src.prev_raw, 0, frame};   // frame -1: the previous batch's last frame
-        out[1] = {images, frame, total - frame};
-        return 2;
-    }
-    if (w == FEAT) {
-        const size_t b = feat_bytes(d, dst);
-        if (b == 0) return 0;
-        out[0] = {src.feat_send[k] + (d->pairs() ? 0 : (size_t)dst * feat_cap(d)), 0, b};   // pair split: one slot
-        return 1;
-    }
-    if (w == PAIRB) {
-        const size_t b = pb_bytes(d, dst);
-        if (b == 0) return 0;
-        out[0] = {src.pb_send[k] + (size_t)dst * pb_slot(d), 0, b};
-        return 1;
-    }
-    return 0;
-}
-
-static int exchange(tslam_shard_driver* d, Which w, int k, const uint8_t* const* images) {
-    const int N = d->world;
-    if (w == STATE && !d->gather()) return TSLAM_OK;
-    const bool pairs = d->pairs();
-    auto recv_buf = [&](Rank& r, int src) -> uint8_t* {   // where src's data lands in r's buffers
-        if (w == RAW) return r.raw_recv[k] + (pairs ? 0 : (size_t)src * raw_cap(d));   // pair split: the partner's
-        if (w == FEAT) return r.feat_recv[k] + (pairs ? 0 : (size_t)src * feat_cap(d));
-        if (w == PAIRB) return r.pb_recv[k] + (size_t)src * pb_slot(d);
-        return r.state_buf[k] + (size_t)src * d->state_cap;
-    };
-    auto recv_bytes = [&](const Rank& r, int src) -> size_t {   // what r receives from src
-        if (w == RAW) return raw_bytes(d, r.rank);
-        if (w == FEAT) return feat_bytes(d, r.rank);
-        if (w == PAIRB) return pb_bytes(d, r.rank);
-        return (size_t)tslam_internal_state_bytes(r.h, d->n, src, src * d->S, (src + 1) * d->S);
-    };
-    // the (src, dst) pairs exchange w connects
-    auto linked = [&](int src, int dst) -> bool {
-        if (w == PAIRB) return pair_peer(d, src, dst);
-        if (w == RAW || (w == FEAT && !d->rgbd)) return stereo_peer(d, src, dst);
-        return src != dst;
-    };
-    if (d->transport == TSLAM_TRANSPORT_RCCL) {
+static int exchange(tslam_shard_driver* d, int w, int k, const uint8_t* const* images) {
+    const XGeom& g = d->g;
+    if (d->transport == TSLAM_TRANSPORT_RCCL) {   // every local rank's operations, in plan order
+        ncclResult_t send_recv = ncclSuccess;
         NCCLCHK(ncclGroupStart());
         for (size_t i = 0; i < d->ranks.size(); ++i) {
             Rank& r = d->ranks[i];
             hipStream_t s = xstream(d, r, w);
-            if (w == POSE) {
-                NCCLCHK(ncclAllGather(r.pose_send[k], r.pose_recv[k], (size_t)d->maxr * d->rec, ncclUint8, r.comm_p, s));
+            if (w == X_POSE) {
+                NCCLCHK(ncclAllGather(r.send[w][k], r.recv[w][k], xp_pose_bytes(g), ncclUint8, r.comm_p, s));
                 continue;
             }
-            if (w == STATE) {   // every rank to rank 0
-                if (r.rank != 0) {
-                    const size_t b = recv_bytes(d->ranks[i], r.rank);
-                    if (b) NCCLCHK(ncclSend(r.state_buf[k], b, ncclUint8, 0, r.comm_p, s));
-                } else {
-                    for (int q = 1; q < N; ++q) {
-                        const size_t b = recv_bytes(r, q);
-                        if (b) NCCLCHK(ncclRecv(recv_buf(r, q), b, ncclUint8, q, r.comm_p, s));
-                    }
-                }
-                continue;
-            }
-            ncclComm_t comm = w == PAIRB ? r.comm_p : r.comm_x;   // PAIRB: the back stream's communicator
-            for (int q = 0; q < N; ++q) {
-                if (!linked(r.rank, q)) continue;
-                Piece pc[2];
-                const int np = pieces(d, r, q, w, k, images ? images[i] : nullptr, pc);
-                for (int j = 0; j < np; ++j) NCCLCHK(ncclSend(pc[j].p, pc[j].bytes, ncclUint8, q, comm, s));
-                // what q sends me, in the same pieces (q's view of my range)
-                const size_t b = recv_bytes(r, q);
-                if (b == 0) continue;
-                int lo, hi;
-                back_range(d, r.rank, &lo, &hi);
-                if (w == RAW && lo == 0) {
-                    const size_t frame = (size_t)d->S * d->img;
-                    NCCLCHK(ncclRecv(recv_buf(r, q), frame, ncclUint8, q, comm, s));
-                    NCCLCHK(ncclRecv(recv_buf(r, q) + frame, b - frame, ncclUint8, q, comm, s));
-                } else {
-                    NCCLCHK(ncclRecv(recv_buf(r, q), b, ncclUint8, q, comm, s));
-                }
-            }
+            xp_ops(g, w, r.rank, [&](const XOp& o) {
+                uint8_t* p = buffer(r, w, o.buf, k, images[i]) + o.off;
+                ncclComm_t comm = o.comm == XC_P ? r.comm_p : r.comm_x;
+                if (send_recv != ncclSuccess) return;
+                send_recv = o.send ? ncclSend(p, o.bytes, ncclUint8, o.peer, comm, s) : ncclRecv(p, o.bytes, ncclUint8, o.peer, comm, s);
+            });
         }
+        NCCLCHK(send_recv);
         NCCLCHK(ncclGroupEnd());
         return TSLAM_OK;
     }
-    // COPY: each sender pushes into its peers' receive buffers on its own exchange-side stream,
-    // once the peer has consumed the previous use of that parity; the receivers wait for every push
+    // COPY: each sender pushes its sends into its peers' receive buffers on its own exchange-side
+    // stream, once the peer has consumed that parity's previous use (its imports of batch s-2; on the
+    // back stream, the end of its batch s-1); the receivers wait for every push
+    hipError_t copy = hipSuccess;
     for (size_t i = 0; i < d->ranks.size(); ++i) {
         Rank& src = d->ranks[i];
         SHCHK(hipSetDevice(src.device));
         hipStream_t s = xstream(d, src, w);
         for (Rank& dst : d->ranks) {
-            if (w == POSE) {
-                if (dst.done_armed && &dst != &src) SHCHK(hipStreamWaitEvent(s, dst.ev_done, 0));
-                SHCHK(hipMemcpyAsync(dst.pose_recv[k] + (size_t)src.rank * d->maxr * d->rec, src.pose_send[k],
-                                     (size_t)d->maxr * d->rec, hipMemcpyDeviceToDevice, s));
-                continue;
-            }
-            if (&dst == &src) continue;
-            if (w == STATE) {
-                if (dst.rank != 0) continue;
-                if (dst.done_armed) SHCHK(hipStreamWaitEvent(s, dst.ev_done, 0));   // rank 0 unpacked batch s-2
-                const size_t b = recv_bytes(dst, src.rank);
-                if (b) SHCHK(hipMemcpyAsync(recv_buf(dst, src.rank), src.state_buf[k], b, hipMemcpyDeviceToDevice, s));
-                continue;
-            }
-            if (!linked(src.rank, dst.rank)) continue;
-            if (w == PAIRB) {   // dst's back stream unpacked this parity's blocks (batch s-2) before its batch s-1 ended
-                if (dst.done_armed) SHCHK(hipStreamWaitEvent(s, dst.ev_done, 0));
-                Piece pc[2];
-                if (pieces(d, src, dst.rank, w, k, nullptr, pc))
-                    SHCHK(hipMemcpyAsync(recv_buf(dst, src.rank), pc[0].p, pc[0].bytes, hipMemcpyDeviceToDevice, s));
-                continue;
-            }
-            if (dst.consumed_armed[k]) SHCHK(hipStreamWaitEvent(s, dst.consumed[k], 0));
-            Piece pc[2];
-            const int np = pieces(d, src, dst.rank, w, k, images ? images[i] : nullptr, pc);
-            for (int j = 0; j < np; ++j)
-                SHCHK(hipMemcpyAsync(recv_buf(dst, src.rank) + pc[j].off, pc[j].p, pc[j].bytes, hipMemcpyDeviceToDevice, s));
+            if (!xp_linked(g, w, src.rank, dst.rank)) continue;
+            if (w <= X_FEAT ? dst.consumed_armed[k] : dst.done_armed && &dst != &src)
+                SHCHK(hipStreamWaitEvent(s, w <= X_FEAT ? dst.consumed[k] : dst.ev_done, 0));
+            xp_sends(g, w, src.rank, dst.rank, [&](const XOp& o) {
+                if (copy == hipSuccess)
+                    copy = hipMemcpyAsync(dst.recv[w][k] + o.dst_off, buffer(src, w, o.buf, k, images[i]) + o.off, o.bytes,
+                                        hipMemcpyDeviceToDevice, s);
+            });
+            SHCHK(copy);
         }
         SHCHK(hipEventRecord(src.ev_push, s));
     }
     for (Rank& dst : d->ranks) {
-        if (w == STATE && dst.rank != 0) continue;
+        if (w == X_STATE && dst.rank != 0) continue;
         SHCHK(hipSetDevice(dst.device));
         hipStream_t s = xstream(d, dst, w);
         for (Rank& src : d->ranks)
@@ -475,12 +305,12 @@ static int exchange(tslam_shard_driver* d, Which w, int k, const uint8_t* const*
 }
 
 static int submit(tslam_shard_driver* d, const uint8_t* const* images, int n, void* const* streams) {
-    if (n < 1 || n > d->B) return tslam_internal_fail(TSLAM_EINVAL, "a sharded batch needs 1 <= n_frames <= max_batch");
-    RC(setup_gather(d));
-    RC(setup_pairs(d));
-    d->n = n;
-    d->maxr = peer_records(n, d->world);
-    const int k = (int)(d->batches & 1), N = d->world, S = d->S;
+    if (n < 1 || n > d->g.B) return tslam_internal_fail(TSLAM_EINVAL, "a sharded batch needs 1 <= n_frames <= max_batch");
+    RC(setup_option(d, X_STATE, d->g.gather));
+    RC(setup_option(d, X_PAIRB, d->g.pairs));
+    d->g.n = n;
+    const XGeom& g = d->g;
+    const int k = (int)(d->batches & 1), N = g.world, S = g.S;
     const bool prof = (d->flags & TSLAM_SHARD_PROFILE) != 0;
     // TSLAM_SHARD_SOLO: rank 0's work only, no exchange (the receive buffers keep what the last
     // full batch left): rank 0's step on a GPU of its own with the exchange hidden
@@ -497,12 +327,12 @@ static int submit(tslam_shard_driver* d, const uint8_t* const* images, int n, vo
             for (hipStream_t s : {FS(d, r), XS(d, r)}) SHCHK(hipStreamWaitEvent(s, r.consumed[k], 0));
         RC(tslam_begin_batch(r.h, images[i], n));
     }
-    if (!d->rgbd && xchg) RC(exchange(d, RAW, k, images));   // straight from the inputs
+    if (!g.rgbd && xchg) RC(exchange(d, X_RAW, k, images));   // straight from the inputs
     for (size_t i = 0; i < d->ranks.size(); ++i) {   // this batch's last frame becomes prev_raw (after the sends)
         Rank& r = d->ranks[i];
-        if (d->rgbd || idle(r)) continue;
+        if (g.rgbd || idle(r)) continue;
         SHCHK(hipSetDevice(r.device));
-        const size_t frame = (size_t)S * d->img;
+        const size_t frame = (size_t)S * g.img;
         SHCHK(hipMemcpyAsync(r.prev_raw, images[i] + (size_t)(n - 1) * frame, frame, hipMemcpyDeviceToDevice, XS(d, r)));
     }
     for (Rank& r : d->ranks) {   // front end of the rank's cameras (+ its stream blocks per peer)
@@ -515,21 +345,21 @@ static int submit(tslam_shard_driver* d, const uint8_t* const* images, int n, vo
         } else {
             for (int st : {TSLAM_STAGE_RECTIFY, TSLAM_STAGE_DETECT, TSLAM_STAGE_DESCRIBE}) RC(tslam_run_stage(r.h, st, FS(d, r)));
         }
-        if (d->rgbd) continue;
+        if (g.rgbd) continue;
         if (N > 1) {
             RC(span_begin(d, r, TSLAM_SEG_PACK, FS(d, r)));
-            if (d->pairs()) RC(tslam_internal_pack_partner(r.h, r.feat_send[k], FS(d, r)));   // the partner's half
-            else RC(tslam_pack_streams_peers(r.h, r.feat_send[k], FS(d, r)));   // every peer's frames, one launch
+            if (g.pairs) RC(tslam_internal_pack_partner(r.h, r.send[X_FEAT][k], FS(d, r)));   // the partner's half
+            else RC(tslam_pack_streams_peers(r.h, r.send[X_FEAT][k], FS(d, r)));   // every peer's frames, one launch
             RC(span_end(d, r, FS(d, r)));
         }
         SHCHK(hipSetDevice(r.device));
         SHCHK(hipEventRecord(r.ev_front, FS(d, r)));
         SHCHK(hipStreamWaitEvent(XS(d, r), r.ev_front, 0));
     }
-    if (!d->rgbd && xchg) RC(exchange(d, FEAT, k, images));
+    if (!g.rgbd && xchg) RC(exchange(d, X_FEAT, k, images));
     for (Rank& r : d->ranks) {   // back end
         if (idle(r)) continue;
-        if (!d->rgbd) {
+        if (!g.rgbd) {
             // the other cameras of frames lo-1 .. hi-1 of this rank's range into the ring
             SHCHK(hipSetDevice(r.device));
             SHCHK(hipEventRecord(r.ev_x, XS(d, r)));
@@ -537,8 +367,8 @@ static int submit(tslam_shard_driver* d, const uint8_t* const* images, int n, vo
             if (prof && N > 1) RC(span_between(d, r, TSLAM_SEG_EXCHANGE_WAIT, FS(d, r), BS(d, r)));   // front done -> data landed
             if (N > 1) {
                 RC(span_begin(d, r, TSLAM_SEG_IMPORT, BS(d, r)));
-                if (d->pairs()) RC(tslam_internal_import_partner(r.h, r.raw_recv[k], r.feat_recv[k], BS(d, r)));
-                else RC(tslam_import_peers(r.h, r.raw_recv[k], r.feat_recv[k], BS(d, r)));
+                if (g.pairs) RC(tslam_internal_import_partner(r.h, r.recv[X_RAW][k], r.recv[X_FEAT][k], BS(d, r)));
+                else RC(tslam_import_peers(r.h, r.recv[X_RAW][k], r.recv[X_FEAT][k], BS(d, r)));
                 RC(span_end(d, r, BS(d, r)));
             }
             SHCHK(hipEventRecord(r.consumed[k], BS(d, r)));
@@ -548,56 +378,58 @@ static int submit(tslam_shard_driver* d, const uint8_t* const* images, int n, vo
             RC(run_timed(d, r, TSLAM_SEG_MATCH, TSLAM_KERNEL_MATCH, BS(d, r)));
             RC(run_timed(d, r, TSLAM_SEG_MATCH_REFINE, TSLAM_KERNEL_MATCH_REFINE, BS(d, r)));
             RC(run_timed(d, r, TSLAM_SEG_POSE, TSLAM_KERNEL_POSE, BS(d, r)));
-            if (d->rig && !d->rgbd && !d->pairs()) RC(run_timed(d, r, TSLAM_SEG_RIG, TSLAM_KERNEL_RIG, BS(d, r)));
+            if (d->rig && !g.rgbd && !g.pairs) RC(run_timed(d, r, TSLAM_SEG_RIG, TSLAM_KERNEL_RIG, BS(d, r)));
         } else {
             RC(tslam_run_stage(r.h, TSLAM_STAGE_MATCH, BS(d, r)));
             RC(tslam_run_stage(r.h, TSLAM_STAGE_POSE, BS(d, r)));
         }
-        if (d->rgbd)   // this rank's cameras over every peer's frame range
+        if (g.rgbd)   // this rank's cameras over every peer's frame range
             for (int q = 0; q < N; ++q) {
-                int lo, hi;
-                peer_range(q, n, N, &lo, &hi);
-                if (q != r.rank && hi > lo)
-                    RC(tslam_pack_pairs(r.h, lo, hi - lo, r.rank * S, (r.rank + 1) * S, r.feat_send[k] + (size_t)q * feat_cap(d),
-                                        BS(d, r)));
+                int lo;
+                const int nf = xp_rig_range(g, q, &lo);
+                if (q != r.rank && nf > 0)
+                    RC(tslam_pack_pairs(r.h, lo, nf, r.rank * S, (r.rank + 1) * S,
+                                        r.send[X_FEAT][k] + xp_slot_off(g, X_FEAT, XB_SEND, q), BS(d, r)));
             }
     }
-    if (d->rgbd) {
-        if (xchg) RC(exchange(d, FEAT, k, images));
+    if (g.rgbd) {
+        if (xchg) RC(exchange(d, X_FEAT, k, images));
         for (Rank& r : d->ranks) {
             if (idle(r)) continue;
-            int lo, hi;
-            peer_range(r.rank, n, N, &lo, &hi);
+            int lo;
+            const int nf = xp_rig_range(g, r.rank, &lo);
             for (int q = 0; q < N; ++q)
-                if (q != r.rank && hi > lo)
-                    RC(tslam_unpack_pairs(r.h, lo, hi - lo, q * S, (q + 1) * S, r.feat_recv[k] + (size_t)q * feat_cap(d), BS(d, r)));
+                if (q != r.rank && nf > 0)
+                    RC(tslam_unpack_pairs(r.h, lo, nf, q * S, (q + 1) * S, r.recv[X_FEAT][k] + xp_slot_off(g, X_FEAT, XB_RECV, q),
+                                          BS(d, r)));
             SHCHK(hipSetDevice(r.device));
             SHCHK(hipEventRecord(r.consumed[k], BS(d, r)));
             r.consumed_armed[k] = true;
             if (d->rig) RC(run_timed(d, r, TSLAM_SEG_RIG, TSLAM_KERNEL_RIG, BS(d, r)));
         }
     }
-    if (d->pairs()) {   // every pair's blocks of a rank's rig range from the ranks of its half, then the rig pose
-        const size_t slot = pb_slot(d);
-        if (d->P > 1) {
+    if (g.pairs) {   // every pair's blocks of a rank's rig range from the ranks of its half, then the rig pose
+        if (g.P > 1) {
             for (Rank& r : d->ranks) {
                 if (idle(r)) continue;
                 RC(span_begin(d, r, TSLAM_SEG_PAIR_BLOCKS, BS(d, r)));
                 for (int q = 0; q < N; ++q) {
-                    int lo, hi;
-                    rig_range(d, q, &lo, &hi);
-                    if (pair_peer(d, r.rank, q) && hi > lo)
-                        RC(tslam_pack_pairs(r.h, lo, hi - lo, r.rank / 2, r.rank / 2 + 1, r.pb_send[k] + (size_t)q * slot, BS(d, r)));
+                    int lo;
+                    const int nf = xp_rig_range(g, q, &lo);
+                    if (xp_linked(g, X_PAIRB, r.rank, q) && nf > 0)
+                        RC(tslam_pack_pairs(r.h, lo, nf, r.rank / 2, r.rank / 2 + 1,
+                                            r.send[X_PAIRB][k] + xp_slot_off(g, X_PAIRB, XB_SEND, q), BS(d, r)));
                 }
             }
-            if (!solo) RC(exchange(d, PAIRB, k, images));
+            if (!solo) RC(exchange(d, X_PAIRB, k, images));
             for (Rank& r : d->ranks) {
                 if (idle(r)) continue;
-                int lo, hi;
-                rig_range(d, r.rank, &lo, &hi);
+                int lo;
+                const int nf = xp_rig_range(g, r.rank, &lo);
                 for (int q = 0; q < N; ++q)
-                    if (pair_peer(d, q, r.rank) && hi > lo)
-                        RC(tslam_unpack_pairs(r.h, lo, hi - lo, q / 2, q / 2 + 1, r.pb_recv[k] + (size_t)q * slot, BS(d, r)));
+                    if (xp_linked(g, X_PAIRB, q, r.rank) && nf > 0)
+                        RC(tslam_unpack_pairs(r.h, lo, nf, q / 2, q / 2 + 1, r.recv[X_PAIRB][k] + xp_slot_off(g, X_PAIRB, XB_RECV, q),
+                                              BS(d, r)));
                 RC(span_end(d, r, BS(d, r)));
             }
         }
@@ -605,37 +437,38 @@ static int submit(tslam_shard_driver* d, const uint8_t* const* images, int n, vo
             for (Rank& r : d->ranks)
                 if (!idle(r)) RC(run_timed(d, r, TSLAM_SEG_RIG, TSLAM_KERNEL_RIG, BS(d, r)));
     }
-    if (d->gather()) {   // every rank's share of the pairs' state into rank 0's ring
+    if (g.gather) {   // every rank's share of the pairs' state into rank 0's ring
         for (Rank& r : d->ranks) {
             if (r.rank == 0 || idle(r)) continue;
             RC(span_begin(d, r, TSLAM_SEG_STATE, BS(d, r)));
-            RC(tslam_internal_state_blocks(r.h, 1, r.rank, r.rank * S, (r.rank + 1) * S, r.state_buf[k], BS(d, r)));
+            RC(tslam_internal_state_blocks(r.h, 1, r.rank, r.rank * S, (r.rank + 1) * S, r.send[X_STATE][k], BS(d, r)));
             RC(span_end(d, r, BS(d, r)));
         }
-        if (!solo) RC(exchange(d, STATE, k, images));
+        if (!solo) RC(exchange(d, X_STATE, k, images));
         for (Rank& r : d->ranks) {
             if (r.rank != 0) continue;
             RC(span_begin(d, r, TSLAM_SEG_STATE, BS(d, r)));
             for (int q = 1; q < N; ++q)
-                RC(tslam_internal_state_blocks(r.h, 0, q, q * S, (q + 1) * S, r.state_buf[k] + (size_t)q * d->state_cap, BS(d, r)));
+                RC(tslam_internal_state_blocks(r.h, 0, q, q * S, (q + 1) * S, r.recv[X_STATE][k] + xp_slot_off(g, X_STATE, XB_RECV, q),
+                                               BS(d, r)));
             RC(span_end(d, r, BS(d, r)));
         }
     }
     for (Rank& r : d->ranks) {
         if (idle(r)) continue;
-        RC(tslam_pack_poses(r.h, r.pose_send[k], BS(d, r)));
+        RC(tslam_pack_poses(r.h, r.send[X_POSE][k], BS(d, r)));
         RC(span_begin(d, r, TSLAM_SEG_POSE_GATHER, BS(d, r)));
     }
-    if (!solo) RC(exchange(d, POSE, k, images));
+    if (!solo) RC(exchange(d, X_POSE, k, images));
     for (size_t i = 0; i < d->ranks.size(); ++i) {
         Rank& r = d->ranks[i];
         if (idle(r)) continue;
         RC(span_end(d, r, BS(d, r)));
-        RC(tslam_unpack_poses(r.h, r.pose_recv[k], BS(d, r)));
+        RC(tslam_unpack_poses(r.h, r.recv[X_POSE][k], BS(d, r)));
         RC(run_timed(d, r, TSLAM_SEG_CHAIN, TSLAM_KERNEL_CHAIN, BS(d, r)));
         // local BA on rank 0 once its ring holds every pair (the back stream keeps it ordered before
         // the next batch's imports; tslam_run_stage orders it after the next-but-one front end)
-        if (d->ba && (r.rank == 0 || N == 1) && (d->gather() || N == 1))
+        if (d->ba && (r.rank == 0 || N == 1) && (g.gather || N == 1))
             RC(run_timed(d, r, TSLAM_SEG_BA, TSLAM_STAGE_BA, BS(d, r)));
         if (d->flags & TSLAM_SHARD_RESULTS) RC(tslam_internal_stash(r.h, BS(d, r)));
         RC(tslam_end_batch(r.h));
@@ -691,7 +524,7 @@ int tslam_comm_init(tslam_handle* h, const void* id128, int rank, int world) {
     if (world < 1 || rank < 0 || rank >= world) return tslam_internal_fail(TSLAM_EINVAL, "need 0 <= rank < world");
     auto* d = new tslam_shard_driver();
     int rc = plan(d, h, world);
-    if (rc == TSLAM_OK) rc = tslam_set_shard(h, rank * d->S, (rank + 1) * d->S, rank, world);
+    if (rc == TSLAM_OK) rc = tslam_set_shard(h, rank * d->g.S, (rank + 1) * d->g.S, rank, world);
     if (rc != TSLAM_OK) {
         delete d;
         return rc;
@@ -712,7 +545,7 @@ int tslam_comm_init(tslam_handle* h, const void* id128, int rank, int world) {
     }
     if (rc == TSLAM_OK) rc = tslam_internal_attach_driver(h, d, true);
     if (rc != TSLAM_OK) {
-        (void)tslam_set_shard(h, 0, (int)(d->S * world), 0, 1);
+        (void)tslam_set_shard(h, 0, (int)(d->g.S * world), 0, 1);
         destroy_driver(d);
     }
     return rc;
@@ -733,11 +566,11 @@ int tslam_shard_options(tslam_handle* h, int flags) {
     if (flags & ~(TSLAM_SHARD_GATHER | TSLAM_SHARD_RESULTS | TSLAM_SHARD_PROFILE | TSLAM_SHARD_SERIAL |
                   TSLAM_SHARD_PIPELINE | TSLAM_SHARD_SOLO | TSLAM_SHARD_PAIRS))
         return tslam_internal_fail(TSLAM_EINVAL, "unknown TSLAM_SHARD_* flag");
-    if ((flags & TSLAM_SHARD_SOLO) && (int)d->ranks.size() != d->world)
+    if ((flags & TSLAM_SHARD_SOLO) && (int)d->ranks.size() != d->g.world)
         return tslam_internal_fail(TSLAM_EINVAL, "TSLAM_SHARD_SOLO needs every rank in this process (tslam_group_create)");
-    if ((flags & TSLAM_SHARD_GATHER) && d->rgbd)
+    if ((flags & TSLAM_SHARD_GATHER) && d->g.rgbd)
         return tslam_internal_fail(TSLAM_EINVAL, "the state gather describes a stereo rig");
-    if ((flags & TSLAM_SHARD_PAIRS) && (d->rgbd || d->S != 1 || d->world < 2))
+    if ((flags & TSLAM_SHARD_PAIRS) && (d->g.rgbd || d->g.S != 1 || d->g.world < 2))
         return tslam_internal_fail(TSLAM_EINVAL, "the pair split shards a stereo rig with one camera per rank");
     if ((flags & TSLAM_SHARD_PAIRS) && (d->ba || (flags & TSLAM_SHARD_GATHER)))
         return tslam_internal_fail(TSLAM_EINVAL, "the pair split runs without the state gather (no local BA)");
@@ -759,7 +592,7 @@ int tslam_shard_options(tslam_handle* h, int flags) {
             }
         }
     for (Rank& r : d->ranks) RC(tslam_internal_set_pairs(r.h, (flags & TSLAM_SHARD_PAIRS) ? 1 : 0));
-    d->flags = flags;
+    d->set_flags(flags);
     return TSLAM_OK;
 }
 
@@ -807,7 +640,7 @@ int tslam_group_create(tslam_handle* const* handles, int n, int transport, tslam
     for (int i = 0; i < n && rc == TSLAM_OK; ++i) {
         d->ranks[i].h = handles[i];
         d->ranks[i].rank = i;
-        rc = tslam_set_shard(handles[i], i * d->S, (i + 1) * d->S, i, n);
+        rc = tslam_set_shard(handles[i], i * d->g.S, (i + 1) * d->g.S, i, n);
         if (rc == TSLAM_OK) rc = setup_rank(d, d->ranks[i]);
     }
     if (rc == TSLAM_OK && transport == TSLAM_TRANSPORT_RCCL) {
@@ -846,7 +679,7 @@ int tslam_group_submit(tslam_group* g, const uint8_t* const* images, int n_frame
 int tslam_group_destroy(tslam_group* g) {
     if (!g) return TSLAM_OK;
     if (g->d) {
-        const int C = g->d->S * g->d->world;
+        const int C = g->d->g.S * g->d->g.world;
         for (Rank& r : g->d->ranks) {
             (void)tslam_internal_attach_driver(r.h, nullptr, false);
             (void)tslam_set_shard(r.h, 0, C, 0, 1);
