@@ -815,7 +815,41 @@ int tslam_esdf_slice(tslam_handle* h, int y0, int y1, double max_dist, double si
  * tslam_stereo_depth_filter_apply: the enabled filters and the depth on caller-supplied dense
  *   device planes of disp32, u16 [n_frames][height][width] (16 .. the handle's size each; values
  *   above 8191 count as 8191), into slots 0 .. n_frames - 1: a disparity from elsewhere is cleaned
- *   this way.  TSLAM_ESTATE unless the filters are on. */
+ *   this way.  TSLAM_ESTATE unless the filters are on.
+ * tslam_stereo_depth_slots (added within ABI 21: a new symbol, nothing else changes):
+ *   tslam_stereo_depth writing slots first_slot .. first_slot + n_frames - 1 (tslam_stereo_depth is
+ *   its first_slot = 0 case); first_slot < 0 or first_slot + n_frames > max_frames: TSLAM_EINVAL.
+ *   Depth and disp32 of every other slot keep their contents, so several pairs' depth of the same
+ *   frames can sit side by side for tslam_tsdf_integrate_rig.
+ * tslam_tsdf_integrate_rig (added within ABI 21: a new symbol and a struct, nothing else changes):
+ *   depth of n_cams cameras of a rig (tslam_set_rig), n_frames frames each, into the volume in ONE
+ *   read-modify-write, on the rig's BODY pose.  `cams` names pairs in strictly ascending order; view
+ *   v = f * n_cams + ci is integrated in ascending v (frame-major, camera-minor), so a call over a
+ *   batch equals one call per frame.  The volume's frame is unchanged (pair 0's rectified left
+ *   camera at frame 0): with E_p = base_T_rect[p] and T = world_T_base of frame f (base at frame
+ *   0), world_T_cam = (E_0^-1 T) E_pair, every product summed in the order
+ *   ((a0 b0 + a1 b1) + a2 b2) + a3 b3.  world_T_base [n_frames][16] on the host, where a NaN in
+ *   element 0 skips all views of that frame; or NULL: the last batch's device-resident body poses
+ *   (frames first_frame .. must belong to it, as for tslam_tsdf_integrate), where a frame is used
+ *   when the rig's status is 0 (tracked) or it is the global first frame.  Per camera: the pair's
+ *   intrinsics, the raw camera's undistortion table (rect 0) or none (rect 1: depth of the
+ *   rectified camera, what tslam_stereo_depth_slots writes), its own depth base and stride, and
+ *   optionally BGR colour for the colour layer.  More than 256 views go in chunks of
+ *   floor(256 / n_cams) whole frames, in order, on the one stream.  TSLAM_ESTATE without
+ *   tslam_set_rig, without a volume, or inside a batch; TSLAM_EINVAL for n_cams outside 1..8, pairs
+ *   not strictly ascending or out of range, a null depth pointer, a stride below one image while
+ *   n_frames > 1, colour pointers mixed null and non-null, or colour without the colour layer.  A
+ *   refused call changes nothing. */
+typedef struct {
+    int32_t pair;          /* the camera: this pair's left (RGB-D: colour) camera */
+    int32_t rect;          /* 0: depth in the raw camera (undistortion table); 1: in the rectified camera */
+    const void* depth;     /* device u16 mm [n_frames][H][W], frame f at depth + f * stride_bytes */
+    const void* color;     /* device BGR u8, same stride, or NULL (all cameras or none) */
+    int64_t stride_bytes;
+} tslam_tsdf_rig_camera;
+int tslam_tsdf_integrate_rig(tslam_handle* h, const tslam_tsdf_rig_camera* cams, int n_cams, int n_frames,
+                             int64_t first_frame, const double* world_T_base, void* stream);
+int tslam_stereo_depth_slots(tslam_handle* h, int pair, int64_t first_frame, int n_frames, int first_slot, void* stream);
 typedef struct {
     int32_t n_disp, uniqueness, lr_tol, reserved;
 } tslam_stereo_depth_params;

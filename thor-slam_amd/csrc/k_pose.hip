@@ -12,6 +12,7 @@
 // correspondences (wave-uniform addresses -> broadcast loads).  Phase C: block argmax, then
 // Gauss-Newton with a block reduction of the 6x6 normal equations per iteration.
 #include "tslam_common.h"
+#include "tslam_mul4.h"
 
 #define P3P_VMAX 1000.0
 #define P3P_BISECT 60
@@ -1075,13 +1076,7 @@ __global__ __launch_bounds__(256) void k_chain(BatchCtx c) {
 // of all pairs together (re-selected every iteration, A7's left-multiplied Cayley update applied to
 // the body motion): with Y = E_q Xc the body point, d(res)/d(rho, omega) = [q, Y x q] where
 // q = dpi/dXc R_e^T.  Covariance sigma^2 H^-1 in the body frame.
-__device__ __forceinline__ void mul4_fixed(const double* A, const double* B, double* out) {
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j)
-            out[4 * i + j] = ((A[4 * i] * B[j] + A[4 * i + 1] * B[4 + j]) + A[4 * i + 2] * B[8 + j]) + A[4 * i + 3] * B[12 + j];
-}
-
-#define TS_RIG_MAXP 8
+// (mul4_fixed: tslam_mul4.h; TS_RIG_MAXP: tslam_common.h)
 // 512 threads (8 waves) per frame: the kernel is a per-frame latency chain (scoring, then 8
 // Gauss-Newton sweeps over every pair's correspondences with a block reduction and a 6x6 solve
 // each); 198 VGPRs fit 2 waves per SIMD, and each thread's share of the sweeps halves

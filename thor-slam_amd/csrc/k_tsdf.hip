@@ -16,7 +16,17 @@
 //                     the undistortion table, truncated signed distance, weighted average;
 //                     with the colour layer, the same pixel's colour averaged into the voxels
 //                     inside the truncation band (nvblox's colour integration).
+//
+// A rig (tslam_tsdf_integrate_rig) integrates several cameras in the same launch:
+//   k_tsdf_rig_poses         per view v = f * n_cams + ci: world_T_cam = (E_0^-1 T_abs(f)) E_pair from
+//                            the rig's body pose (device record or staged host poses), inverted;
+//   k_tsdf_integrate<true>   the same kernel walking views instead of frames, the view's camera
+//                            (intrinsics, table, depth / colour base and stride) from a per-camera
+//                            record in the kernel argument, read with scalar loads.
+#include <type_traits>
+
 #include "tslam_common.h"
+#include "tslam_mul4.h"
 
 // host poses: world_T_cam [n][16] -> cam_T_world; device poses: T_abs of batch frames (f0 + i)
 __global__ void k_tsdf_poses(BatchCtx c, int pair, int f0, const double* host_wTc, int n, double* out) {
@@ -41,6 +51,35 @@ __global__ void k_tsdf_poses(BatchCtx c, int pair, int f0, const double* host_wT
     q[12] = use;
 }
 
+// rig: view v = f * n_cams + ci on the body pose T = world_T_base(f) (base at frame 0), in the
+// volume's frame (pair 0's rectified left camera at frame 0): world_T_cam = (E_0^-1 T) E_pair, the
+// products in mul4_fixed's order, then k_tsdf_poses' inverse.  A frame's views are all used or all
+// skipped: the rig's status (k_rig_pose: 0 tracked, 2 at the global first frame), or a NaN host pose.
+__global__ void k_tsdf_rig_poses(BatchCtx c, uint64_t pairs, int n_cams, int f0, const double* host_wTb, int n, double* out) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n) return;
+    const int f = v / n_cams, pair = (int)((pairs >> (8 * (v % n_cams))) & 0xff);
+    const double* Tb;
+    double use = 1.0;
+    if (host_wTb) {
+        Tb = host_wTb + 16 * (size_t)f;
+        use = __builtin_isfinite(Tb[0]) ? 1.0 : 0.0;
+    } else {
+        Tb = c.rig_pose + (size_t)(f0 + f) * TS_POSE_DOUBLES + 16;
+        const int st = c.rig_stats[(size_t)(f0 + f) * TS_STATS_INTS];
+        use = (st == 0 || (st == 2 && c.g0 + f0 + f == 0)) ? 1.0 : 0.0;
+    }
+    double A[16], T[16];
+    mul4_fixed(c.rig_Einv, Tb, A);
+    mul4_fixed(A, c.rig_E + 16 * pair, T);
+    double* q = out + (size_t)v * TSDF_POSE;
+    for (int r = 0; r < 3; ++r) {
+        for (int k = 0; k < 3; ++k) q[3 * r + k] = T[4 * k + r];   // R^T
+        q[9 + r] = -((T[r] * T[3] + T[4 + r] * T[7]) + T[8 + r] * T[11]);
+    }
+    q[12] = use;
+}
+
 // Bricks of 16 x 4 x 4 voxels, one per 256-thread block (x rows of 64 B stay coalesced).  Before
 // touching a voxel the block decides, one frame per thread, which frames can see ANY voxel of its
 // brick: the brick's bounding sphere against the conditions the per-voxel test applies
@@ -53,8 +92,8 @@ __global__ void k_tsdf_poses(BatchCtx c, int pair, int f0, const double* host_wT
 #define TSDF_BY 4
 #define TSDF_BZ 4
 
-__device__ __forceinline__ bool tsdf_brick_visible(const TsdfArgs& a, const double* q, double X, double Y, double Z,
-                                                   double R) {
+__device__ __forceinline__ bool tsdf_brick_visible(const TsdfArgs& a, double fx, double fy, double cx, double cy,
+                                                   const double* q, double X, double Y, double Z, double R) {
     if (q[12] == 0.0) return false;
     const double pz = ((q[6] * X + q[7] * Y) + q[8] * Z) + q[11];
     if (pz + R <= 0.0) return false;                      // every voxel has p_z <= 0
@@ -62,15 +101,19 @@ __device__ __forceinline__ bool tsdf_brick_visible(const TsdfArgs& a, const doub
     const double px = ((q[0] * X + q[1] * Y) + q[2] * Z) + q[9];
     const double py = ((q[3] * X + q[4] * Y) + q[5] * Z) + q[10];
     // u + 1/2 >= 0  <=>  fx p_x + (cx + 1/2) p_z >= 0;  u + 1/2 < W  <=>  fx p_x + (cx + 1/2 - W) p_z < 0
-    const double cl = a.cx + 0.5, cr = a.cx + 0.5 - a.W, ct = a.cy + 0.5, cb = a.cy + 0.5 - a.H;
-    if (a.fx * px + cl * pz + R * sqrt(a.fx * a.fx + cl * cl) < 0.0) return false;
-    if (a.fx * px + cr * pz - R * sqrt(a.fx * a.fx + cr * cr) >= 0.0) return false;
-    if (a.fy * py + ct * pz + R * sqrt(a.fy * a.fy + ct * ct) < 0.0) return false;
-    if (a.fy * py + cb * pz - R * sqrt(a.fy * a.fy + cb * cb) >= 0.0) return false;
+    const double cl = cx + 0.5, cr = cx + 0.5 - a.W, ct = cy + 0.5, cb = cy + 0.5 - a.H;
+    if (fx * px + cl * pz + R * sqrt(fx * fx + cl * cl) < 0.0) return false;
+    if (fx * px + cr * pz - R * sqrt(fx * fx + cr * cr) >= 0.0) return false;
+    if (fy * py + ct * pz + R * sqrt(fy * fy + ct * ct) < 0.0) return false;
+    if (fy * py + cb * pz - R * sqrt(fy * fy + cb * cb) >= 0.0) return false;
     return true;
 }
 
-__global__ __launch_bounds__(256) void k_tsdf_integrate(TsdfArgs a, int nbx, int nby) {
+// RIG: a.n views (frame-major, camera-minor) instead of a.n frames of one camera.  The view index
+// in the update loop is wave-uniform (it comes from the block's mask words), so the view's camera
+// record is read from the kernel argument with scalar loads, once per (brick, view).
+template <bool RIG>
+__global__ __launch_bounds__(256) void k_tsdf_integrate(std::conditional_t<RIG, TsdfRigArgs, TsdfArgs> a, int nbx, int nby) {
     __shared__ double s_p[TSDF_MAX_FRAMES * TSDF_POSE];
     __shared__ uint64_t s_mask[TSDF_MAX_FRAMES / 64];
     for (int i = threadIdx.x; i < a.n * TSDF_POSE; i += blockDim.x) s_p[i] = a.poses[i];
@@ -85,7 +128,12 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate(TsdfArgs a, int nbx, int
             const double BX = a.ox + a.s * (i0 + 0.5 * ex), BY = a.oy + a.s * (j0 + 0.5 * ey),
                          BZ = a.oz + a.s * (k0 + 0.5 * ez);
             const double R = 0.5 * a.s * sqrt((double)(ex * ex + ey * ey + ez * ez)) * 1.01 + 1e-6;
-            vis = tsdf_brick_visible(a, s_p + t * TSDF_POSE, BX, BY, BZ, R);
+            if constexpr (RIG) {
+                const TsdfRigCam& cm = a.cams[t % a.n_cams];
+                vis = tsdf_brick_visible(a, cm.fx, cm.fy, cm.cx, cm.cy, s_p + t * TSDF_POSE, BX, BY, BZ, R);
+            } else {
+                vis = tsdf_brick_visible(a, a.fx, a.fy, a.cx, a.cy, s_p + t * TSDF_POSE, BX, BY, BZ, R);
+            }
         }
         const uint64_t m = __ballot(vis);
         if ((t & 63) == 0) s_mask[t >> 6] = m;
@@ -102,23 +150,40 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate(TsdfArgs a, int nbx, int
     for (int wd = 0; wd < (a.n + 63) / 64; ++wd) {
         uint64_t m = s_mask[wd];   // wave-uniform: frames in order
         while (m) {
-            const int f = wd * 64 + __builtin_ctzll(m);
+            int f = wd * 64 + __builtin_ctzll(m);
             m &= m - 1;
+            double fx, fy, cx, cy;
+            const int32_t* map;
+            const uint8_t *depth, *color;
+            if constexpr (RIG) {   // f is a view: its frame's image of its camera
+                f = __builtin_amdgcn_readfirstlane(f);
+                const TsdfRigCam& cm = a.cams[f % a.n_cams];
+                const size_t fo = (size_t)(f / a.n_cams) * cm.stride;
+                fx = cm.fx, fy = cm.fy, cx = cm.cx, cy = cm.cy;
+                map = cm.map;
+                depth = cm.depth + fo;
+                color = cm.color + fo;
+            } else {
+                fx = a.fx, fy = a.fy, cx = a.cx, cy = a.cy;
+                map = a.map;
+                depth = a.depth + (size_t)f * a.stride;
+                color = a.color + (size_t)f * a.stride;
+            }
             const double* q = s_p + f * TSDF_POSE;   // LDS broadcast
             const double pz = ((q[6] * X + q[7] * Y) + q[8] * Z) + q[11];
             if (!(pz > 0.0)) continue;
             const double px = ((q[0] * X + q[1] * Y) + q[2] * Z) + q[9];
             const double py = ((q[3] * X + q[4] * Y) + q[5] * Z) + q[10];
-            const double u = a.fx * px / pz + a.cx, vv = a.fy * py / pz + a.cy;
+            const double u = fx * px / pz + cx, vv = fy * py / pz + cy;
             const double fu = floor(u + 0.5), fv = floor(vv + 0.5);
             if (!(fu >= 0.0 && fu < a.W && fv >= 0.0 && fv < a.H)) continue;
             int ix = (int)fu, iy = (int)fv;
-            if (a.map) {
-                const int32_t* mp = a.map + ((size_t)iy * a.W + ix) * 2;
+            if (map) {
+                const int32_t* mp = map + ((size_t)iy * a.W + ix) * 2;
                 ix = min(max((mp[0] + 16) >> 5, 0), a.W - 1);
                 iy = min(max((mp[1] + 16) >> 5, 0), a.H - 1);
             }
-            const uint16_t mm = reinterpret_cast<const uint16_t*>(a.depth + (size_t)f * a.stride)[(size_t)iy * a.W + ix];
+            const uint16_t mm = reinterpret_cast<const uint16_t*>(depth)[(size_t)iy * a.W + ix];
             const double d = (double)mm * 0.001;
             if (!(d > 0.0 && d <= a.max_dist)) continue;
             const double sdf = d - pz;
@@ -139,7 +204,7 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate(TsdfArgs a, int nbx, int
             ts = (double)(float)((ts * w + obs) / w1);   // stored as f32 after every frame (as the oracle)
             w = (double)(float)fmin(w1, a.max_weight);
             if (a.col && sdf <= a.trunc) {   // colour inside the truncation band: the same pixel's BGR
-                const uint8_t* px = a.color + (size_t)f * a.stride + ((size_t)iy * a.W + ix) * 3;
+                const uint8_t* px = color + ((size_t)iy * a.W + ix) * 3;
                 const double c1 = cw + 1.0;
                 cr = (double)(float)((cr * cw + (double)px[2]) / c1);
                 cg = (double)(float)((cg * cw + (double)px[1]) / c1);
@@ -167,5 +232,15 @@ void launch_tsdf(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev
     b.poses = poses;
     const int nbx = (a.nx + TSDF_BX - 1) / TSDF_BX, nby = (a.ny + TSDF_BY - 1) / TSDF_BY,
               nbz = (a.nz + TSDF_BZ - 1) / TSDF_BZ;
-    hipLaunchKernelGGL(k_tsdf_integrate, dim3((unsigned)((int64_t)nbx * nby * nbz)), dim3(256), 0, s, b, nbx, nby);
+    hipLaunchKernelGGL(k_tsdf_integrate<false>, dim3((unsigned)((int64_t)nbx * nby * nbz)), dim3(256), 0, s, b, nbx, nby);
+}
+
+void launch_tsdf_rig(const BatchCtx& c, uint64_t pairs, int f0, const double* host_wTb_dev, const TsdfRigArgs& a,
+                     double* poses, hipStream_t s) {
+    hipLaunchKernelGGL(k_tsdf_rig_poses, dim3((a.n + 63) / 64), dim3(64), 0, s, c, pairs, a.n_cams, f0, host_wTb_dev, a.n, poses);
+    TsdfRigArgs b = a;
+    b.poses = poses;
+    const int nbx = (a.nx + TSDF_BX - 1) / TSDF_BX, nby = (a.ny + TSDF_BY - 1) / TSDF_BY,
+              nbz = (a.nz + TSDF_BZ - 1) / TSDF_BZ;
+    hipLaunchKernelGGL(k_tsdf_integrate<true>, dim3((unsigned)((int64_t)nbx * nby * nbz)), dim3(256), 0, s, b, nbx, nby);
 }

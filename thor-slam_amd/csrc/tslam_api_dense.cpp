@@ -137,6 +137,75 @@ int tslam_tsdf_integrate_rect(tslam_handle* h, int pair, const void* depth, int6
     return tsdf_integrate(h, pair, nullptr, depth, stride_bytes, n_frames, first_frame, world_T_cam, stream, true);
 }
 
+// Several cameras of a rig in one launch per chunk, on the body pose (k_tsdf.hip, launch_tsdf_rig).
+int tslam_tsdf_integrate_rig(tslam_handle* h, const tslam_tsdf_rig_camera* cams, int n_cams, int n_frames,
+                             int64_t first_frame, const double* world_T_base, void* stream) {
+    if (!h || !cams) return fail(TSLAM_EINVAL, "bad argument");
+    BA_FLUSH(h);
+    if (!h->rig) return fail(TSLAM_ESTATE, "no rig set (tslam_set_rig)");
+    if (!h->tsdf_on) return fail(TSLAM_ESTATE, "no TSDF volume (tslam_tsdf_init)");
+    if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_tsdf_integrate_rig inside a batch");
+    if (n_cams < 1 || n_cams > TS_RIG_MAXP) return fail(TSLAM_EINVAL, "n_cams must be 1..8");
+    if (n_frames < 0) return fail(TSLAM_EINVAL, "n_frames must be >= 0");
+    const bool color = cams[0].color != nullptr;
+    for (int ci = 0; ci < n_cams; ++ci) {
+        const tslam_tsdf_rig_camera& cm = cams[ci];
+        if (cm.pair < 0 || cm.pair >= h->P || (ci > 0 && cm.pair <= cams[ci - 1].pair))
+            return fail(TSLAM_EINVAL, "pairs must be strictly ascending and in range");
+        if (!cm.depth || (n_frames > 1 && cm.stride_bytes < 2LL * h->W * h->H)) return fail(TSLAM_EINVAL, "bad depth / stride");
+        if ((cm.color != nullptr) != color) return fail(TSLAM_EINVAL, "colour for all cameras or for none");
+    }
+    if (color && !h->tsdf_color) return fail(TSLAM_EINVAL, "colour without the colour layer (tslam_tsdf_color)");
+    int f0 = 0;
+    if (!world_T_base) {   // device poses: frames of the last batch
+        f0 = (int)(first_frame - h->cur_g0);
+        if (first_frame < h->cur_g0 || f0 + n_frames > h->cur_n)
+            return fail(TSLAM_EINVAL, "device poses: frames must belong to the last batch");
+    }
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = stream ? (hipStream_t)stream : h->last_stream;
+    const BatchCtx c = make_ctx(h);
+    TsdfRigArgs a{};
+    static_cast<TsdfArgs&>(a) = h->tsdf;
+    a.W = h->W;
+    a.H = h->H;
+    a.n_cams = n_cams;
+    if (!color) a.col = a.col_w = nullptr;   // the colour layer keeps its state without colour input
+    uint64_t pairs = 0;
+    for (int ci = 0; ci < n_cams; ++ci) {
+        const int pair = cams[ci].pair, cam = c.cpp * pair;
+        pairs |= (uint64_t)pair << (8 * ci);
+        TsdfRigCam& r = a.cams[ci];
+        r.fx = h->calib[pair].fx;
+        r.fy = h->calib[pair].fy;
+        r.cx = h->calib[pair].cx;
+        r.cy = h->calib[pair].cy;
+        r.map = (!cams[ci].rect && ((h->map_mask >> cam) & 1u)) ? h->d_maps + (size_t)cam * h->W * h->H * 2 : nullptr;
+        r.stride = cams[ci].stride_bytes;
+    }
+    // chunks of whole frames, so that every chunk's views fit the pose table and stay frame-major
+    const int chunk = TSDF_MAX_FRAMES / n_cams;
+    for (int b0 = 0; b0 < n_frames; b0 += chunk) {
+        const int nf = std::min(chunk, n_frames - b0);
+        a.n = nf * n_cams;
+        for (int ci = 0; ci < n_cams; ++ci) {
+            const size_t o = (size_t)b0 * cams[ci].stride_bytes;
+            a.cams[ci].depth = static_cast<const uint8_t*>(cams[ci].depth) + o;
+            a.cams[ci].color = color ? static_cast<const uint8_t*>(cams[ci].color) + o : nullptr;
+        }
+        const double* wtb = nullptr;
+        if (world_T_base) {
+            HIPCHK(hipMemcpyAsync(h->d_tsdf_wTc, world_T_base + (size_t)16 * b0, sizeof(double) * 16 * nf,
+                                  hipMemcpyHostToDevice, s));
+            wtb = h->d_tsdf_wTc;
+        }
+        launch_tsdf_rig(c, pairs, f0 + b0, wtb, a, h->d_tsdf_poses, s);
+        HIPCHK(hipGetLastError());
+        if (world_T_base) HIPCHK(hipStreamSynchronize(s));   // the staged host poses are reused
+    }
+    return TSLAM_OK;
+}
+
 // -- dense stereo depth ------------------------------------------------------------------------------
 // the semi-global matcher's scratch (A and S) goes back to the device; the box matcher runs again
 static void sgm_off(tslam_handle* h) {
@@ -191,23 +260,36 @@ int tslam_stereo_depth_init(tslam_handle* h, const tslam_stereo_depth_params* pa
     return TSLAM_OK;
 }
 
-// rules 9 and 10, then rule 8, on the n frames of W x H that lie in the slots
-static int stereo_filter_run(tslam_handle* h, int W, int H, int n, double fxb, hipStream_t s) {
+// rules 9 and 10, then rule 8, on the n frames of W x H that lie in the slots slot0 ..
+//
+// The median's u16 plane lives in d_sd_win, the matcher's call-scoped winner maps (u8, left half
+// then right half, 2 * max_frames planes in all).  The u16 plane of slot s covers the bytes of the
+// u8 planes 2s and 2s + 1, so at a slot offset it lies over winner maps of OTHER slots, and for
+// s >= max_frames / 2 it reaches into the right-winner half.  That is safe: winner maps are
+// written and read inside one matcher call, this filter runs after that call's matcher on the same
+// stream, so every winner map is dead by now; and slot s < max_frames ends at byte
+// 2 (s + 1) W H <= 2 max_frames W H, the size of the allocation.  Nothing a caller reads back lives
+// in d_sd_win; the planes that do (disp32, depth, and the label / count scratch) are indexed by slot.
+static int stereo_filter_run(tslam_handle* h, int W, int H, int n, double fxb, hipStream_t s, int slot0 = 0) {
     const tslam_stereo_depth_filter_params& p = h->sd_flt_prm;
-    const StereoFilterArgs f{W, H, n, fxb, p.median, p.speckle_size, p.speckle_range, h->d_sd_disp, h->d_sd_depth,
-                             reinterpret_cast<uint16_t*>(h->d_sd_win), h->d_sd_label, h->d_sd_count};
+    const size_t so = (size_t)slot0 * W * H;
+    const StereoFilterArgs f{W, H, n, fxb, p.median, p.speckle_size, p.speckle_range, h->d_sd_disp + so, h->d_sd_depth + so,
+                             reinterpret_cast<uint16_t*>(h->d_sd_win) + so, h->d_sd_label ? h->d_sd_label + so : nullptr,
+                             h->d_sd_count ? h->d_sd_count + so : nullptr};
     HIPCHK(launch_sd_filter(f, s));
     return TSLAM_OK;
 }
 
-static int stereo_depth_run(tslam_handle* h, StereoDepthArgs a, void* stream) {
+// the n frames of `a` into slots slot0 .. slot0 + n - 1: every per-slot plane starts slot0 planes in
+static int stereo_depth_run(tslam_handle* h, StereoDepthArgs a, void* stream, int slot0 = 0) {
+    const size_t so = (size_t)slot0 * a.W * a.H;
     a.n_disp = h->sd_prm.n_disp;
     a.uniqueness = h->sd_prm.uniqueness;
     a.lr_tol = h->sd_prm.lr_tol;
-    a.depth = h->d_sd_depth;
-    a.disp32 = h->d_sd_disp;
-    a.win_left = h->d_sd_win;
-    a.win_right = h->d_sd_win + (size_t)h->sd_frames * h->W * h->H;
+    a.depth = h->d_sd_depth + so;
+    a.disp32 = h->d_sd_disp + so;
+    a.win_left = h->d_sd_win + so;
+    a.win_right = h->d_sd_win + (size_t)h->sd_frames * h->W * h->H + so;
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = stream ? (hipStream_t)stream : h->last_stream;
     if (h->sd_sgm_on) {
@@ -232,7 +314,7 @@ static int stereo_depth_run(tslam_handle* h, StereoDepthArgs a, void* stream) {
         HIPCHK(launch_stereo_depth(a, s));
     }
     if (h->sd_flt_on)
-        if (const int rc = stereo_filter_run(h, a.W, a.H, a.n, a.fxb, s); rc != TSLAM_OK) return rc;
+        if (const int rc = stereo_filter_run(h, a.W, a.H, a.n, a.fxb, s, slot0); rc != TSLAM_OK) return rc;
     h->sd_w = a.W;
     h->sd_h = a.H;
     return TSLAM_OK;
@@ -331,11 +413,12 @@ int tslam_stereo_depth_filter_apply(tslam_handle* h, const uint16_t* disp32, int
     return TSLAM_OK;
 }
 
-int tslam_stereo_depth(tslam_handle* h, int pair, int64_t first_frame, int n_frames, void* stream) {
+int tslam_stereo_depth_slots(tslam_handle* h, int pair, int64_t first_frame, int n_frames, int first_slot, void* stream) {
     if (!h || pair < 0 || pair >= h->P) return fail(TSLAM_EINVAL, "bad handle or pair");
     if (!h->sd_on) return fail(TSLAM_ESTATE, "no stereo depth buffers (tslam_stereo_depth_init)");
     if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_stereo_depth inside a batch");
     if (n_frames < 0 || n_frames > h->sd_frames) return fail(TSLAM_EINVAL, "n_frames must be 0..max_frames");
+    if (first_slot < 0 || first_slot + n_frames > h->sd_frames) return fail(TSLAM_EINVAL, "first_slot + n_frames must be within max_frames");
     if (first_frame < h->cur_g0 || first_frame - h->cur_g0 + n_frames > h->cur_n)
         return fail(TSLAM_EINVAL, "frames must belong to the last batch");
     BA_FLUSH(h);
@@ -350,7 +433,11 @@ int tslam_stereo_depth(tslam_handle* h, int pair, int64_t first_frame, int n_fra
     a.H = h->H;
     a.n = n_frames;
     a.fxb = h->calib[pair].fxb;
-    return stereo_depth_run(h, a, stream);
+    return stereo_depth_run(h, a, stream, first_slot);
+}
+
+int tslam_stereo_depth(tslam_handle* h, int pair, int64_t first_frame, int n_frames, void* stream) {
+    return tslam_stereo_depth_slots(h, pair, first_frame, n_frames, 0, stream);
 }
 
 int tslam_stereo_depth_images(tslam_handle* h, const uint8_t* left, const uint8_t* right, int64_t frame_stride, int width,

@@ -303,6 +303,26 @@ struct TsdfArgs {
 };
 void launch_tsdf(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev, const TsdfArgs& a, double* poses,
                  hipStream_t s);
+// The rig's launch: every selected camera of every frame in one read-modify-write of the volume.
+// View v = f * n_cams + ci (frame-major, camera-minor) is integrated in ascending v, on the rig's
+// body pose: world_T_cam = (E_0^-1 T_abs(f)) E_pair.  TsdfArgs' n counts VIEWS here, and its depth /
+// color / stride / map / intrinsics are unused: they come from the view's camera record.
+#define TS_RIG_MAXP 8   // pairs of a rig (tslam_create: n_pairs <= 8)
+struct TsdfRigCam {
+    const uint8_t* depth;      // this camera's frame 0 (u16 mm), frames `stride` bytes apart
+    const uint8_t* color;      // BGR u8 with the same stride (null: TsdfArgs::col is null too)
+    const int32_t* map;        // the raw camera's undistortion table, or null (rectified depth)
+    int64_t stride;
+    double fx, fy, cx, cy;
+};
+struct TsdfRigArgs : TsdfArgs {
+    int n_cams;
+    TsdfRigCam cams[TS_RIG_MAXP];
+};
+// pairs: 8 bits per camera, camera ci's pair in bits 8 ci .. 8 ci + 7; f0: first frame within the batch
+// (device poses); host_wTb_dev: staged world_T_base [n_frames][16] or null
+void launch_tsdf_rig(const BatchCtx& c, uint64_t pairs, int f0, const double* host_wTb_dev, const TsdfRigArgs& a,
+                     double* poses, hipStream_t s);
 // dense stereo depth (k_stereo_depth.hip): n frames of one rectified pair -> disp32 (1/32 px) and
 // depth (mm), u16 [n][H][W]; win_left / win_right: u8 [n][H][W] winner maps between its two kernels
 struct StereoDepthArgs {

@@ -109,6 +109,14 @@ class StereoDepthFilterParams(ctypes.Structure):
     ]
 
 
+class TsdfRigCamera(ctypes.Structure):
+    """tslam_tsdf_rig_camera: one camera of ``Handle.tsdf_integrate_rig``."""
+    _fields_ = [
+        ("pair", ctypes.c_int32), ("rect", ctypes.c_int32), ("depth", ctypes.c_void_p), ("color", ctypes.c_void_p),
+        ("stride_bytes", ctypes.c_int64),
+    ]
+
+
 def camera_desc(cam) -> CameraDesc:
     """A ``CameraConfig`` (intrinsics + world extrinsics) as a ``tslam_camera_desc``."""
     d = CameraDesc()
@@ -282,6 +290,10 @@ _SIGNATURES = {
                                                        ctypes.c_double, ctypes.c_int, ctypes.c_void_p]),
     "tslam_tsdf_integrate_rect": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
                                                  ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "tslam_tsdf_integrate_rig": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                                ctypes.c_void_p, ctypes.c_void_p]),
+    "tslam_stereo_depth_slots": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_void_p]),
 }
 
 
@@ -901,6 +913,24 @@ class Handle:
                                                   int(n_frames), int(first_frame),
                                                   None if poses is None else poses.ctypes.data, ctypes.c_void_p(stream)))
 
+    def tsdf_integrate_rig(self, cams, n_frames: int, first_frame: int = 0, world_T_base: np.ndarray | None = None,
+                           stream: int = 0) -> None:
+        """Depth of several cameras of the rig (``set_rig``) into the volume in one launch, on the
+        rig's body pose (thor_slam_amd/dense.py ``rig_world_T_cam``).  ``cams``: per camera a dict
+        ``pair``, ``depth`` (device pointer, u16 mm), ``stride_bytes``, and optionally ``rect``
+        (depth of the rectified camera) and ``color`` (device pointer, BGR), pairs strictly
+        ascending.  ``world_T_base`` [n_frames][4][4] on the host, or None: the last batch's
+        device-resident body poses of frames first_frame.. ."""
+        arr = (TsdfRigCamera * max(len(cams), 1))()
+        for i, c in enumerate(cams):
+            arr[i] = TsdfRigCamera(int(c["pair"]), int(bool(c.get("rect", False))), int(c["depth"]) or None,
+                                   int(c.get("color") or 0) or None, int(c["stride_bytes"]))
+        poses = None
+        if world_T_base is not None:
+            poses = np.ascontiguousarray(np.asarray(world_T_base, dtype=np.float64).reshape(-1, 4, 4))
+        _check(self.lib.tslam_tsdf_integrate_rig(self.h, ctypes.addressof(arr), len(cams), int(n_frames), int(first_frame),
+                                                 None if poses is None else poses.ctypes.data, ctypes.c_void_p(stream)))
+
     # -- dense stereo depth (thor_slam_amd/stereo_depth.py) ------------------------------------
     def stereo_depth_init(self, max_frames: int = 1, n_disp: int = 0, uniqueness: int = 10, lr_tol: int = 1) -> None:
         """Parameters and output slots of the dense stereo matcher (n_disp 0 = the handle's
@@ -931,9 +961,11 @@ class Handle:
                                                         float(fxb), int(n_frames), ctypes.c_void_p(stream)))
         self._sd_shape = (int(height), int(width))
 
-    def stereo_depth(self, first_frame: int, n_frames: int, pair: int = 0, stream: int = 0) -> None:
-        """Depth of ``pair``'s frames first_frame.. of the last batch into slots 0..n_frames-1."""
-        _check(self.lib.tslam_stereo_depth(self.h, int(pair), int(first_frame), int(n_frames), ctypes.c_void_p(stream)))
+    def stereo_depth(self, first_frame: int, n_frames: int, pair: int = 0, stream: int = 0, first_slot: int = 0) -> None:
+        """Depth of ``pair``'s frames first_frame.. of the last batch into slots first_slot ..
+        first_slot + n_frames - 1 (the other slots keep their depth and disp32)."""
+        _check(self.lib.tslam_stereo_depth_slots(self.h, int(pair), int(first_frame), int(n_frames), int(first_slot),
+                                                 ctypes.c_void_p(stream)))
         self._sd_shape = (self.height, self.width)
 
     def stereo_depth_images(self, left_dev_ptr: int, right_dev_ptr: int, frame_stride: int, width: int, height: int,

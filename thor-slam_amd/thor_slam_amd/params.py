@@ -10,6 +10,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 
+from .dense_rig import DenseCamerasError
 from .slam.interface import SlamConfig
 from .stereo_depth import check_params as check_stereo_depth_params
 from .stereo_depth import check_filter_params as check_stereo_depth_filter_params
@@ -115,10 +116,20 @@ class HipSlamConfig(SlamConfig):
     # input kind: RGB-D (BASELINE configs[4]) = per source a colour camera (cam_idx 0, BGR) and a
     # depth image aligned to it (cam_idx 1, u16 mm); depth replaces stereo matching
     rgbd: bool = False
-    # RGB-D dense mapping: the depth of pair 0 (the reference maps camera_0
-    # only, launch/thor_nvblox.launch.py:50-56) integrated into a dense TSDF volume on the device
-    # with the tracked poses; nvblox's parameters and defaults (thor_nvblox.launch.py:26-36)
+    # RGB-D dense mapping: depth integrated into a dense TSDF volume on the
+    # device with the tracked poses; nvblox's parameters and defaults (thor_nvblox.launch.py:26-36).
+    # The reference's interface is a list of cameras (config/slam_config.yaml:61-68 nvblox_cameras,
+    # of which it ships camera_0 enabled and a second one commented in; scripts/run_pipeline.py:
+    # 371-392 publishes every listed camera; launch/thor_nvblox.launch.py:23 num_cameras).  Here the
+    # default maps pair 0 on pair 0's own pose; dense_cameras below maps a list of them.
     dense_map: bool = False
+    # the rig's cameras that feed the dense map (thor_slam_amd/dense_rig.py): () = pair 0 alone on
+    # its own chained pose; "all", or a tuple of pair indices and / or source names (the reference's
+    # nvblox_cameras entries, matched against CameraConfig.source_name) = those pairs' left (RGB-D:
+    # colour) cameras, every frame of them in one launch, on the rig's BODY pose (the one the
+    # published pose, local BA and loop closure use).  Needs dense_map, a rig of several pairs and
+    # one device; resolved to ascending pair indices at initialize.
+    dense_cameras: tuple | str = ()
     voxel_size: float = 0.05
     tsdf_integrator_max_integration_distance_m: float = 10.0
     tsdf_integrator_truncation_distance_vox: float = 4.0
@@ -205,6 +216,17 @@ class HipSlamConfig(SlamConfig):
                 raise ValueError("voxel_size, integration distance, truncation must be > 0, max weight >= 1")
             if len(self.tsdf_dims) != 3 or min(self.tsdf_dims) < 1 or len(self.tsdf_origin) != 3:
                 raise ValueError("tsdf_dims must be 3 positive voxel counts, tsdf_origin 3 coordinates")
+        if isinstance(self.dense_cameras, str):
+            if self.dense_cameras != "all":
+                raise DenseCamerasError("dense_cameras must be (), 'all' or a tuple of pair indices / source names")
+        elif len(set(self.dense_cameras)) != len(tuple(self.dense_cameras)):
+            raise DenseCamerasError("dense_cameras names a camera twice")
+        if self.dense_cameras:
+            if not self.dense_map:
+                raise DenseCamerasError("dense_cameras needs dense_map=True")
+            if self.devices:
+                # rank 0 holds only its own cameras' records (and pair 0's pose, not the body's)
+                raise DenseCamerasError("dense_cameras does not run on a sharded rig (devices)")
         if not (self.ba_window == 0 or 2 <= self.ba_window <= 10):
             raise ValueError("ba_window must be 0 (off) or in [2, 10]")
         if self.ba_kf_interval < 1 or self.ba_iters < 1:

@@ -29,7 +29,10 @@ volume on the device with the batch's tracked poses (nvblox's role in the refere
 ``scripts/run_pipeline.py:218-256``); ``get_dense_map`` returns it.  On a stereo rig
 ``stereo_depth`` supplies that depth: pair 0's rectified images go through the dense stereo matcher
 (``thor_slam_amd/stereo_depth.py``) every ``stereo_depth_interval``-th frame, in the same
-synchronous branch; ``get_depth_image`` returns the newest depth image.
+synchronous branch; ``get_depth_image`` returns the newest depth image.  ``dense_cameras`` ("all",
+or pair indices / source names) integrates those cameras of the rig instead, every frame of them
+in one launch per batch (``tslam_tsdf_integrate_rig``) on the rig's body poses, for RGB-D records
+and for dense stereo depth alike (``thor_slam_amd/dense_rig.py``).
 With ``HipSlamConfig(devices=[d0, d1, ...])`` the rig is sharded one camera stream per GPU from
 this one process (cuVSLAM's multicam mode, launch/thor_visual_slam.launch.py:49,81):
 one handle per device, driven by the library as one sharded rig (``tslam_group_*``: an RCCL clique
@@ -62,6 +65,7 @@ from .._lib import POSE_INIT, POSE_LOST, POSE_OK, Handle, HandleGroup, SingularS
 from ..calib import (StereoRectification, confidence_from_covariance, extract_cameras, rgbd_pairs, rgbd_undistort,
                      stereo_pairs, stereo_rectify)
 from ..camera.rig import RigCalibration
+from ..dense_rig import DenseCamerasError, resolve_dense_cameras
 from ..loop import span_edges
 from ..camera.types import SynchronizedFrameSet
 from ..imu import ImuNoise, ImuPropagator, vision_only
@@ -451,7 +455,8 @@ class HipSlamEngine(SlamEngine):
         self._loop: _LoopGraph | None = None     # set up by initialize() when loop closure is on
         self._in_flight = 0                       # batches submitted, not yet published
         self._shard: dict | None = None           # sharded rig (config.devices): handles, group, inputs
-        self._sd_last: tuple | None = None        # (slot, timestamp) of the newest stereo depth image
+        self._sd_last: dict = {}                  # pair -> (slot, timestamp) of its newest stereo depth image
+        self._dense_pairs: tuple = ()             # config.dense_cameras resolved (() = pair 0 on its own pose)
 
     # ------------------------------------------------------------------------------------------
     def initialize(self, calibration: RigCalibration, config: SlamConfig | None = None) -> None:
@@ -473,6 +478,8 @@ class HipSlamEngine(SlamEngine):
                 if not self._pairs:
                     raise RuntimeError("HipSlamEngine needs at least one stereo source (cam_idx 0 and 1)")
                 self._rects = [stereo_rectify(self._cameras[l], self._cameras[r]) for l, r in self._pairs]
+            # the cameras of the dense map (config.dense_cameras): ascending pair indices
+            self._dense_pairs = resolve_dense_cameras(cfg.dense_cameras, [self._cameras[l].source_name for l, _ in self._pairs])
             import torch  # PyTorch is the device-memory / stream plumbing only
 
             if not torch.cuda.is_available():
@@ -518,15 +525,16 @@ class HipSlamEngine(SlamEngine):
                 self._handle.tsdf_init(cfg.tsdf_origin, cfg.tsdf_dims, cfg.voxel_size,
                                        cfg.tsdf_integrator_truncation_distance_vox,
                                        cfg.tsdf_integrator_max_integration_distance_m, cfg.tsdf_max_weight)
-                if cfg.stereo_depth:   # a stereo rig: pair 0's depth comes from the dense matcher
-                    self._handle.stereo_depth_init(max_frames=cfg.batch_size, uniqueness=cfg.stereo_depth_uniqueness,
+                if cfg.stereo_depth:   # a stereo rig: the depth comes from the dense matcher (slots per camera)
+                    self._handle.stereo_depth_init(max_frames=cfg.batch_size * max(1, len(self._dense_pairs)),
+                                                   uniqueness=cfg.stereo_depth_uniqueness,
                                                    lr_tol=cfg.stereo_depth_lr_tol)
                     if cfg.stereo_depth_sgm:
                         self._handle.stereo_depth_sgm(p1=cfg.stereo_depth_p1, p2=cfg.stereo_depth_p2)
                     if cfg.stereo_depth_median or cfg.stereo_depth_speckle_size:
                         self._handle.stereo_depth_filter(median=cfg.stereo_depth_median, speckle_size=cfg.stereo_depth_speckle_size,
                                                          speckle_range=cfg.stereo_depth_speckle_range)
-            self._sd_last = None   # (slot, timestamp) of the newest stereo depth image
+            self._sd_last = {}
             self._loop = None
             if cfg.enable_loop_closure and cfg.devices and cfg.rgbd:
                 # rank 0's ring holds only its own cameras' features (no state gather): no rig-wide
@@ -547,7 +555,7 @@ class HipSlamEngine(SlamEngine):
                     self._loop = _AsyncLoop(self._handle, cfg, len(self._pairs), m)
                 else:
                     self._loop = _LoopGraph()
-        except RuntimeError:
+        except (RuntimeError, DenseCamerasError):
             raise
         except Exception as exc:  # per interface.py:187-188
             raise RuntimeError(f"HipSlamEngine initialisation failed: {exc}") from exc
@@ -949,9 +957,12 @@ class HipSlamEngine(SlamEngine):
         tracked poses (untracked frames are skipped), on the batch's stream.  ``cams_per_frame``: the
         records per frame of the buffer (a sharded rig: rank 0's cameras, pair 0 first).  With
         ``stereo_depth`` the depth of the batch's frames g with g % stereo_depth_interval == 0 is
-        first computed from pair 0's rectified images (k_stereo_depth.hip), in the rectified camera."""
+        first computed from pair 0's rectified images (k_stereo_depth.hip), in the rectified camera.
+        With ``dense_cameras`` the selected pairs' depth (records, or stereo depth in slots ci m ..)
+        goes in by one ``tsdf_integrate_rig`` per run of frames, on the rig's body poses."""
         if not self._config.dense_map:
             return
+        dense = self._dense_pairs
         if self._config.stereo_depth:
             g0 = self._handle.frames_done - n
             every = self._config.stereo_depth_interval
@@ -959,13 +970,28 @@ class HipSlamEngine(SlamEngine):
             # one launch per run of consecutive frames (the whole batch at interval 1)
             runs = [(g0, n)] if every == 1 else [(g, 1) for g in range(g0, g0 + n) if g % every == 0]
             for g, m in runs:
+                stamp = None if stamps is None else float(stamps[g + m - 1 - g0])
+                if dense:   # camera ci's run in slots ci m .., then every camera's views in one launch
+                    for ci, p in enumerate(dense):
+                        self._handle.stereo_depth(g, m, pair=p, stream=stream, first_slot=ci * m)
+                        self._sd_last[p] = (ci * m + m - 1, stamp)
+                    self._handle.tsdf_integrate_rig(
+                        [dict(pair=p, rect=True, depth=depth_ptr + ci * m * frame_bytes, stride_bytes=frame_bytes)
+                         for ci, p in enumerate(dense)], m, first_frame=g, stream=stream)
+                    continue
                 self._handle.stereo_depth(g, m, pair=0, stream=stream)
                 self._handle.tsdf_integrate_rect(depth_ptr, frame_bytes, m, first_frame=g, pair=0, stream=stream)
-                self._sd_last = (m - 1, None if stamps is None else float(stamps[g + m - 1 - g0]))
+                self._sd_last[0] = (m - 1, stamp)
             return
         r = self._rects[0]
         hw = r.width * r.height
         stride = 5 * hw * (cams_per_frame or len(self._pairs))
+        if dense:   # the selected cameras' parts of the batch's records, on the rig's body poses
+            self._handle.tsdf_integrate_rig(
+                [dict(pair=p, depth=records_ptr + p * 5 * hw + 3 * hw, stride_bytes=stride,
+                      color=records_ptr + p * 5 * hw if self._dense_color else None) for p in dense],
+                n, first_frame=self._handle.frames_done - n, stream=stream)
+            return
         if self._dense_color:   # the record's BGR part with its depth part
             self._handle.tsdf_integrate_rgbd(records_ptr, records_ptr + 3 * hw, stride, n,
                                              first_frame=self._handle.frames_done - n, pair=0, stream=stream)
@@ -973,16 +999,16 @@ class HipSlamEngine(SlamEngine):
             self._handle.tsdf_integrate(records_ptr + 3 * hw, stride, n,
                                         first_frame=self._handle.frames_done - n, pair=0, stream=stream)
 
-    def get_depth_image(self) -> tuple | None:
-        """(depth u16 [H][W] in mm of pair 0's rectified left camera, timestamp) of the newest frame
-        the dense stereo matcher processed, or None (``stereo_depth`` with ``dense_map`` only).
-        Synchronises."""
+    def get_depth_image(self, pair: int = 0) -> tuple | None:
+        """(depth u16 [H][W] in mm of pair ``pair``'s rectified left camera, timestamp) of the newest
+        frame the dense stereo matcher processed for that pair (pair 0, or any pair of
+        ``dense_cameras``), or None (``stereo_depth`` with ``dense_map`` only).  Synchronises."""
         if self._handle is None or not (self._config.stereo_depth and self._config.dense_map):
             return None
         self.flush()
-        if self._sd_last is None:
+        if int(pair) not in self._sd_last:
             return None
-        slot, stamp = self._sd_last
+        slot, stamp = self._sd_last[int(pair)]
         return self._handle.stereo_depth_read(slot)[0], stamp
 
     def get_dense_map(self) -> dict | None:
@@ -1410,7 +1436,7 @@ class HipSlamEngine(SlamEngine):
         self._imu_seq = 0
         self._kf_imu = None
         self._kf_ine = None
-        self._sd_last = None
+        self._sd_last = {}
         if self._imu is not None:
             self._imu.reset()
         self._keyframe_poses = []
