@@ -872,6 +872,34 @@ int tslam_stereo_depth_read(tslam_handle* h, int slot, uint16_t* depth, uint16_t
 int tslam_tsdf_integrate_rect(tslam_handle* h, int pair, const void* depth, int64_t stride_bytes, int n_frames,
                               int64_t first_frame, const double* world_T_cam, void* stream);
 
+/* The rolling window of the dense map (added within ABI 21: three new symbols and a struct; nothing
+ * else changes, and a handle that calls none of them behaves as before).  Spec:
+ * thor_slam_amd/dense_follow.py.  The volume keeps its size and moves in whole voxels: a cumulative
+ * shift[3] (0 after tslam_tsdf_init and tslam_reset) gives the effective origin
+ * origin[a] + voxel_size * (double)shift[a], which integration, the mesh, and the reads and writes
+ * of the volume then refer to.  A move by delta keeps new(i, j, k) = old(i + dx, j + dy, k + dz)
+ * where that voxel exists and zeroes every other voxel of every layer.
+ *
+ * tslam_tsdf_follow: with params, every tslam_tsdf_integrate* call decides once, on the device and
+ *   before its first voxel update, from the first used view of its first chunk of 256 views: the
+ *   voxel c that holds the camera centre, e = c - anchor per axis, and where |e| > margin a move
+ *   of step * trunc(e / step) voxels (C division).  No used view, a centre that is not finite, or
+ *   an index or shift that would reach 2^30 moves nothing.  One decision per call: the result
+ *   depends on how frames are grouped into calls.  NULL turns following off; the window stays
+ *   where it is.  TSLAM_EINVAL unless 1 <= step <= margin < 2^30 and |anchor| < 2^30; TSLAM_ESTATE
+ *   without a volume.  Allocates a scratch copy of the volume.  tslam_tsdf_init turns it off.
+ * tslam_tsdf_shift: move the window by delta[3] voxels (|delta| < 2^30), asynchronously on
+ *   `stream` (NULL: the handle's last stream), with following on or off; a saved window is
+ *   restored by shifting the empty volume and then writing it (tslam_tsdf_write).
+ * tslam_tsdf_window: the current shift and effective origin (either may be NULL; synchronises). */
+typedef struct {
+    int32_t anchor[3];     /* the voxel of the window the camera centre is kept near */
+    int32_t margin, step;  /* voxels */
+} tslam_tsdf_follow_params;
+int tslam_tsdf_follow(tslam_handle* h, const tslam_tsdf_follow_params* params);
+int tslam_tsdf_shift(tslam_handle* h, const int32_t* delta, void* stream);
+int tslam_tsdf_window(tslam_handle* h, int32_t* shift, double* origin);
+
 #ifdef __cplusplus
 }
 #endif

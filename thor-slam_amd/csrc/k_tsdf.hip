@@ -23,6 +23,16 @@
 //   k_tsdf_integrate<true>   the same kernel walking views instead of frames, the view's camera
 //                            (intrinsics, table, depth / colour base and stride) from a per-camera
 //                            record in the kernel argument, read with scalar loads.
+//
+// The rolling window (thor_slam_amd/dense_follow.py; opt-in, tslam_tsdf_follow / tslam_tsdf_shift):
+//   k_tsdf_follow     one wave: the first used entry of the call's first pose table, the camera
+//                     centre's voxel against the anchor, and from that the call's move (delta) and
+//                     the new cumulative shift, into the handle's TsdfWindow record;
+//   k_tsdf_shift      the same two fields from a caller's delta;
+//   k_tsdf_move       every layer of the volume moved by delta into the scratch, and (a second
+//                     launch) copied back; both return at once when delta is zero;
+//   k_tsdf_integrate  with TsdfArgs::win set, the volume's corner is o + s * (double)shift.
+#include <algorithm>
 #include <type_traits>
 
 #include "tslam_common.h"
@@ -117,6 +127,12 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate(std::conditional_t<RIG, 
     __shared__ double s_p[TSDF_MAX_FRAMES * TSDF_POSE];
     __shared__ uint64_t s_mask[TSDF_MAX_FRAMES / 64];
     for (int i = threadIdx.x; i < a.n * TSDF_POSE; i += blockDim.x) s_p[i] = a.poses[i];
+    double ox = a.ox, oy = a.oy, oz = a.oz;
+    if (a.win) {   // the rolling window: the corner from the cumulative shift (three uniform loads)
+        ox = a.ox + a.s * (double)a.win->shift[0];
+        oy = a.oy + a.s * (double)a.win->shift[1];
+        oz = a.oz + a.s * (double)a.win->shift[2];
+    }
     const int b = blockIdx.x;
     const int i0 = (b % nbx) * TSDF_BX, j0 = ((b / nbx) % nby) * TSDF_BY, k0 = (b / (nbx * nby)) * TSDF_BZ;
     const int ex = min(TSDF_BX, a.nx - i0), ey = min(TSDF_BY, a.ny - j0), ez = min(TSDF_BZ, a.nz - k0);
@@ -125,8 +141,8 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate(std::conditional_t<RIG, 
         const int t = threadIdx.x;
         bool vis = false;
         if (t < a.n) {
-            const double BX = a.ox + a.s * (i0 + 0.5 * ex), BY = a.oy + a.s * (j0 + 0.5 * ey),
-                         BZ = a.oz + a.s * (k0 + 0.5 * ez);
+            const double BX = ox + a.s * (i0 + 0.5 * ex), BY = oy + a.s * (j0 + 0.5 * ey),
+                         BZ = oz + a.s * (k0 + 0.5 * ez);
             const double R = 0.5 * a.s * sqrt((double)(ex * ex + ey * ey + ez * ez)) * 1.01 + 1e-6;
             if constexpr (RIG) {
                 const TsdfRigCam& cm = a.cams[t % a.n_cams];
@@ -143,7 +159,7 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate(std::conditional_t<RIG, 
     if (ti >= ex || tj >= ey || tk >= ez) return;
     const int i = i0 + ti, j = j0 + tj, k = k0 + tk;
     const int64_t v = ((int64_t)k * a.ny + j) * a.nx + i;
-    const double X = a.ox + a.s * (i + 0.5), Y = a.oy + a.s * (j + 0.5), Z = a.oz + a.s * (k + 0.5);
+    const double X = ox + a.s * (i + 0.5), Y = oy + a.s * (j + 0.5), Z = oz + a.s * (k + 0.5);
     bool loaded = false;
     double ts = 0.0, w = 0.0;
     double cr = 0.0, cg = 0.0, cb = 0.0, cw = 0.0;   // colour layer (loaded with the voxel)
@@ -225,9 +241,144 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate(std::conditional_t<RIG, 
     }
 }
 
+// -- the rolling window --------------------------------------------------------------------------
+// The decision of one integrate call (thor_slam_amd/dense_follow.py, "The decision"): one wave.
+// Every lane ends up with the same first used entry (ballot + ctz), so all lanes compute the same
+// move and lane 0 writes it.  No used entry, a centre that is not finite, or an index / shift that
+// would reach 2^30: delta = 0 and the shift stays.
+__global__ __launch_bounds__(64) void k_tsdf_follow(const double* __restrict__ poses, int n, double o0x, double o0y, double o0z,
+                                                    double s, TsdfFollow f, TsdfWindow* win) {
+    const int lane = threadIdx.x;
+    int first = -1;
+    for (int base = 0; base < n; base += 64) {
+        const int i = base + lane;
+        const bool used = i < n && poses[(size_t)i * TSDF_POSE + 12] != 0.0;
+        const uint64_t m = __ballot(used);
+        if (m) {
+            first = base + __builtin_ctzll(m);
+            break;
+        }
+    }
+    int sh[3], d[3] = {0, 0, 0};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) sh[a] = win->shift[a];
+    if (first >= 0) {
+        const double* q = poses + (size_t)first * TSDF_POSE;
+        const double o0[3] = {o0x, o0y, o0z};
+        bool ok = true;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double C = -((q[a] * q[9] + q[3 + a] * q[10]) + q[6 + a] * q[11]);
+            const double c = floor((C - (o0[a] + s * (double)sh[a])) / s);
+            if (!__builtin_isfinite(C) || !(fabs(c) < (double)TSDF_SHIFT_LIMIT)) {   // a NaN c too
+                ok = false;
+                continue;
+            }
+            const int e = (int)c - f.anchor[a];   // |anchor| < 2^30 (tslam_tsdf_follow): no overflow
+            d[a] = (e > f.margin || e < -f.margin) ? f.step * (e / f.step) : 0;
+            const int64_t ns = (int64_t)sh[a] + d[a];
+            if (ns <= -(int64_t)TSDF_SHIFT_LIMIT || ns >= (int64_t)TSDF_SHIFT_LIMIT) ok = false;
+        }
+        if (!ok) d[0] = d[1] = d[2] = 0;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            win->delta[a] = d[a];
+            win->shift[a] = sh[a] + d[a];
+        }
+    }
+}
+
+// a caller's move: the same two fields (a shift that would reach 2^30 moves nothing)
+__global__ void k_tsdf_shift(TsdfWindow* win, int dx, int dy, int dz) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    int d[3] = {dx, dy, dz};
+    bool ok = true;
+    for (int a = 0; a < 3; ++a) {
+        const int64_t ns = (int64_t)win->shift[a] + d[a];
+        if (ns <= -(int64_t)TSDF_SHIFT_LIMIT || ns >= (int64_t)TSDF_SHIFT_LIMIT) ok = false;
+    }
+    for (int a = 0; a < 3; ++a) {
+        if (!ok) d[a] = 0;
+        win->delta[a] = d[a];
+        win->shift[a] += d[a];
+    }
+}
+
+// One row of L floats: dst[x] = src[x + sx] where the row exists (ok) and 0 <= x + sx < L, else 0.
+// src is the source row's first element (dereferenced only where the element exists).  V: float4
+// (the caller has checked L % 4 == 0 and sx % 4 == 0, and row bases are multiples of L) or float.
+template <typename V>
+__device__ __forceinline__ void tsdf_move_row(V* __restrict__ dst, const V* __restrict__ src, int64_t L, int64_t sx, bool ok,
+                                              int lane) {
+    for (int64_t x = lane; x < L; x += 64) {
+        const int64_t xs = x + sx;
+        V v{};
+        if (ok && xs >= 0 && xs < L) v = src[xs];
+        dst[x] = v;
+    }
+}
+
+// The move, one wave per row (j, k) of every layer, rows grid-strided over a bounded grid.
+// BACK = false: scratch(i, j, k) = vol(i + dx, j + dy, k + dz) inside the volume, else 0;
+// BACK = true: vol = scratch.  delta comes from the record (uniform loads); zero: nothing to do.
+template <bool BACK>
+__global__ __launch_bounds__(256) void k_tsdf_move(TsdfLayers l, const TsdfWindow* __restrict__ win) {
+    const int dx = win->delta[0], dy = win->delta[1], dz = win->delta[2];
+    if ((dx | dy | dz) == 0) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t rows = (int64_t)l.ny * l.nz;
+    const int64_t w0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), wn = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t row = w0; row < rows; row += wn) {
+        int64_t srow = row, sdx = 0;
+        bool ok = true;
+        if (!BACK) {
+            const int64_t k = row / l.ny, j = row - k * l.ny;
+            const int64_t js = j + dy, ks = k + dz;
+            ok = js >= 0 && js < l.ny && ks >= 0 && ks < l.nz;
+            srow = ks * l.ny + js;
+            sdx = dx;
+        }
+        for (int a = 0; a < l.n; ++a) {
+            const int64_t L = (int64_t)l.nx * l.comp[a], sx = sdx * l.comp[a];
+            float* dst = (BACK ? l.vol[a] : l.scratch[a]) + row * L;
+            const float* src = (BACK ? l.scratch[a] : l.vol[a]) + (ok ? srow : 0) * L;
+            if (((L | sx) & 3) == 0)
+                tsdf_move_row(reinterpret_cast<float4*>(dst), reinterpret_cast<const float4*>(src), L >> 2, sx >> 2, ok, lane);
+            else
+                tsdf_move_row(dst, src, L, sx, ok, lane);
+        }
+    }
+}
+
+void launch_tsdf_follow(const double* poses, int n, const TsdfArgs& a, const TsdfFollow& f, TsdfWindow* win, hipStream_t s) {
+    hipLaunchKernelGGL(k_tsdf_follow, dim3(1), dim3(64), 0, s, poses, n, a.ox, a.oy, a.oz, a.s, f, win);
+}
+
+void launch_tsdf_shift(TsdfWindow* win, int dx, int dy, int dz, hipStream_t s) {
+    hipLaunchKernelGGL(k_tsdf_shift, dim3(1), dim3(64), 0, s, win, dx, dy, dz);
+}
+
+// a bounded grid: a call that does not move costs two launches of at most TSDF_MOVE_BLOCKS blocks
+#define TSDF_MOVE_BLOCKS 2048
+void launch_tsdf_move(const TsdfLayers& l, const TsdfWindow* win, hipStream_t s) {
+    const int64_t rows = (int64_t)l.ny * l.nz;
+    const unsigned blocks = (unsigned)std::min<int64_t>((rows + 3) / 4, TSDF_MOVE_BLOCKS);
+    hipLaunchKernelGGL(k_tsdf_move<false>, dim3(blocks), dim3(256), 0, s, l, win);
+    hipLaunchKernelGGL(k_tsdf_move<true>, dim3(blocks), dim3(256), 0, s, l, win);
+}
+
+static void tsdf_follow_call(const TsdfFollowCall* fc, const double* poses, const TsdfArgs& a, hipStream_t s) {
+    if (!fc) return;
+    launch_tsdf_follow(poses, a.n, a, fc->f, fc->win, s);
+    launch_tsdf_move(fc->l, fc->win, s);
+}
+
 void launch_tsdf(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev, const TsdfArgs& a, double* poses,
-                 hipStream_t s) {
+                 hipStream_t s, const TsdfFollowCall* follow) {
     hipLaunchKernelGGL(k_tsdf_poses, dim3((a.n + 63) / 64), dim3(64), 0, s, c, pair, f0, host_wTc_dev, a.n, poses);
+    tsdf_follow_call(follow, poses, a, s);
     TsdfArgs b = a;
     b.poses = poses;
     const int nbx = (a.nx + TSDF_BX - 1) / TSDF_BX, nby = (a.ny + TSDF_BY - 1) / TSDF_BY,
@@ -236,8 +387,9 @@ void launch_tsdf(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev
 }
 
 void launch_tsdf_rig(const BatchCtx& c, uint64_t pairs, int f0, const double* host_wTb_dev, const TsdfRigArgs& a,
-                     double* poses, hipStream_t s) {
+                     double* poses, hipStream_t s, const TsdfFollowCall* follow) {
     hipLaunchKernelGGL(k_tsdf_rig_poses, dim3((a.n + 63) / 64), dim3(64), 0, s, c, pairs, a.n_cams, f0, host_wTb_dev, a.n, poses);
+    tsdf_follow_call(follow, poses, a, s);
     TsdfRigArgs b = a;
     b.poses = poses;
     const int nbx = (a.nx + TSDF_BX - 1) / TSDF_BX, nby = (a.ny + TSDF_BY - 1) / TSDF_BY,

@@ -15,9 +15,63 @@ static int dense_quiesce(tslam_handle* h) {
     return TSLAM_OK;
 }
 
+// -- the rolling window (thor_slam_amd/dense_follow.py) -----------------------------------------
+static size_t align4(size_t n) { return (n + 3) & ~(size_t)3; }
+
+// the record and the move's scratch, on first use and after a larger tslam_tsdf_init
+static int window_alloc(tslam_handle* h) {
+    const size_t nv = tsdf_voxels(h);
+    const size_t floats = 2 * align4(nv) + (h->tsdf.col ? align4(nv) + align4(3 * nv) : 0);
+    int rc = dev_grow(h, (void**)&h->d_tsdf_scratch, sizeof(float) * floats, &h->tsdf_scratch_cap);
+    if (rc == TSLAM_OK && !h->d_tsdf_win) {
+        rc = dev_alloc(h, (void**)&h->d_tsdf_win, sizeof(TsdfWindow));
+        if (rc != TSLAM_OK) return rc;
+        HIPCHK(hipMemset(h->d_tsdf_win, 0, sizeof(TsdfWindow)));
+    }
+    return rc;
+}
+
+static TsdfLayers window_layers(const tslam_handle* h) {
+    const TsdfArgs& t = h->tsdf;
+    const size_t nv = tsdf_voxels(h);
+    TsdfLayers l{};
+    l.nx = t.nx;
+    l.ny = t.ny;
+    l.nz = t.nz;
+    float* s = h->d_tsdf_scratch;
+    auto add = [&](float* vol, int comp) {
+        l.vol[l.n] = vol;
+        l.scratch[l.n] = s;
+        l.comp[l.n++] = comp;
+        s += align4(nv * comp);
+    };
+    add(t.tsdf, 1);
+    add(t.weight, 1);
+    if (t.col) {
+        add(t.col_w, 1);
+        add(t.col, 3);
+    }
+    return l;
+}
+
+// the window as the device has it once `s` has drained: one small copy and a stream synchronise
+// when the record exists, nothing otherwise
+static int window_read(tslam_handle* h, hipStream_t s, int32_t shift[3], double origin[3]) {
+    const TsdfArgs& t = h->tsdf;
+    shift[0] = shift[1] = shift[2] = 0;
+    if (h->d_tsdf_win) {
+        HIPCHK(hipMemcpyAsync(shift, h->d_tsdf_win->shift, sizeof(int32_t) * 3, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    const double o0[3] = {t.ox, t.oy, t.oz};
+    for (int a = 0; a < 3; ++a) origin[a] = h->d_tsdf_win ? o0[a] + t.s * (double)shift[a] : o0[a];
+    return TSLAM_OK;
+}
+
 // tslam_reset: the volume belongs to the session (the stereo depth slots do not: they stay)
 int dense_reset(tslam_handle* h) {
     if (h->tsdf_on) {
+        if (h->d_tsdf_win) HIPCHK(hipMemset(h->d_tsdf_win, 0, sizeof(TsdfWindow)));
         const size_t nv = tsdf_voxels(h);
         HIPCHK(hipMemset(h->tsdf.tsdf, 0, sizeof(float) * nv));
         HIPCHK(hipMemset(h->tsdf.weight, 0, sizeof(float) * nv));
@@ -52,6 +106,8 @@ int tslam_tsdf_init(tslam_handle* h, const double* origin, const int32_t* dims, 
     if (rc == TSLAM_OK && !h->d_tsdf_poses) rc = dev_alloc(h, (void**)&h->d_tsdf_poses, sizeof(double) * TSDF_MAX_FRAMES * TSDF_POSE);
     if (rc == TSLAM_OK && !h->d_tsdf_wTc) rc = dev_alloc(h, (void**)&h->d_tsdf_wTc, sizeof(double) * TSDF_MAX_FRAMES * 16);
     if (rc != TSLAM_OK) return rc;
+    if (h->d_tsdf_win) HIPCHK(hipMemset(h->d_tsdf_win, 0, sizeof(TsdfWindow)));   // a new volume: shift 0, not following
+    h->tsdf_follow_on = false;
     a.nx = dims[0];
     a.ny = dims[1];
     a.nz = dims[2];
@@ -95,6 +151,9 @@ static int tsdf_integrate(tslam_handle* h, int pair, const void* color, const vo
     // rect: the depth lives in the pair's rectified camera already (tslam_stereo_depth)
     a.map = (!rect && ((h->map_mask >> cam) & 1u)) ? h->d_maps + (size_t)cam * h->W * h->H * 2 : nullptr;
     a.stride = stride_bytes;
+    // following: the call's decision and move between chunk 0's poses and its integration
+    a.win = h->d_tsdf_win;   // null unless the window was ever followed or shifted
+    const TsdfFollowCall fc{h->tsdf_follow, h->tsdf_follow_on ? window_layers(h) : TsdfLayers{}, h->d_tsdf_win};
     if (!color) a.col = a.col_w = nullptr;   // the colour layer keeps its state without colour input
     for (int b0 = 0; b0 < n_frames; b0 += TSDF_MAX_FRAMES) {
         a.n = std::min(TSDF_MAX_FRAMES, n_frames - b0);
@@ -106,9 +165,59 @@ static int tsdf_integrate(tslam_handle* h, int pair, const void* color, const vo
                                   hipMemcpyHostToDevice, s));
             wtc = h->d_tsdf_wTc;
         }
-        launch_tsdf(c, pair, f0 + b0, wtc, a, h->d_tsdf_poses, s);
+        launch_tsdf(c, pair, f0 + b0, wtc, a, h->d_tsdf_poses, s, h->tsdf_follow_on && b0 == 0 ? &fc : nullptr);
         HIPCHK(hipGetLastError());
         if (world_T_cam) HIPCHK(hipStreamSynchronize(s));   // the staged host poses are reused
+    }
+    return TSLAM_OK;
+}
+
+int tslam_tsdf_follow(tslam_handle* h, const tslam_tsdf_follow_params* p) {
+    if (!h) return fail(TSLAM_EINVAL, "null handle");
+    BA_FLUSH(h);
+    if (!h->tsdf_on) return fail(TSLAM_ESTATE, "no TSDF volume (tslam_tsdf_init)");
+    if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_tsdf_follow inside a batch");
+    if (!p) {   // off: the window stays where it is
+        h->tsdf_follow_on = false;
+        return TSLAM_OK;
+    }
+    if (p->step < 1 || p->margin < p->step || p->margin >= TSDF_SHIFT_LIMIT) return fail(TSLAM_EINVAL, "need 1 <= step <= margin < 2^30");
+    for (int a = 0; a < 3; ++a)
+        if (p->anchor[a] <= -TSDF_SHIFT_LIMIT || p->anchor[a] >= TSDF_SHIFT_LIMIT) return fail(TSLAM_EINVAL, "|anchor| must be below 2^30");
+    HIPCHK(hipSetDevice(h->device));
+    if (const int rc = window_alloc(h); rc != TSLAM_OK) return rc;
+    h->tsdf_follow = TsdfFollow{{p->anchor[0], p->anchor[1], p->anchor[2]}, p->margin, p->step};
+    h->tsdf_follow_on = true;
+    return TSLAM_OK;
+}
+
+int tslam_tsdf_shift(tslam_handle* h, const int32_t* delta, void* stream) {
+    if (!h || !delta) return fail(TSLAM_EINVAL, "bad argument");
+    BA_FLUSH(h);
+    if (!h->tsdf_on) return fail(TSLAM_ESTATE, "no TSDF volume (tslam_tsdf_init)");
+    if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_tsdf_shift inside a batch");
+    for (int a = 0; a < 3; ++a)
+        if (delta[a] <= -TSDF_SHIFT_LIMIT || delta[a] >= TSDF_SHIFT_LIMIT) return fail(TSLAM_EINVAL, "|delta| must be below 2^30");
+    HIPCHK(hipSetDevice(h->device));
+    if (const int rc = window_alloc(h); rc != TSLAM_OK) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : h->last_stream;
+    launch_tsdf_shift(h->d_tsdf_win, delta[0], delta[1], delta[2], s);
+    launch_tsdf_move(window_layers(h), h->d_tsdf_win, s);
+    HIPCHK(hipGetLastError());
+    h->esdf_valid = false;
+    return TSLAM_OK;
+}
+
+int tslam_tsdf_window(tslam_handle* h, int32_t* shift, double* origin) {
+    if (!h || !h->tsdf_on) return fail(TSLAM_ESTATE, "no TSDF volume (tslam_tsdf_init)");
+    BA_FLUSH(h);
+    if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
+    int32_t sh[3];
+    double o[3];
+    if (const int rc = window_read(h, h->last_stream, sh, o); rc != TSLAM_OK) return rc;
+    for (int a = 0; a < 3; ++a) {
+        if (shift) shift[a] = sh[a];
+        if (origin) origin[a] = o[a];
     }
     return TSLAM_OK;
 }
@@ -170,6 +279,8 @@ int tslam_tsdf_integrate_rig(tslam_handle* h, const tslam_tsdf_rig_camera* cams,
     a.W = h->W;
     a.H = h->H;
     a.n_cams = n_cams;
+    a.win = h->d_tsdf_win;
+    const TsdfFollowCall fc{h->tsdf_follow, h->tsdf_follow_on ? window_layers(h) : TsdfLayers{}, h->d_tsdf_win};
     if (!color) a.col = a.col_w = nullptr;   // the colour layer keeps its state without colour input
     uint64_t pairs = 0;
     for (int ci = 0; ci < n_cams; ++ci) {
@@ -199,7 +310,7 @@ int tslam_tsdf_integrate_rig(tslam_handle* h, const tslam_tsdf_rig_camera* cams,
                                   hipMemcpyHostToDevice, s));
             wtb = h->d_tsdf_wTc;
         }
-        launch_tsdf_rig(c, pairs, f0 + b0, wtb, a, h->d_tsdf_poses, s);
+        launch_tsdf_rig(c, pairs, f0 + b0, wtb, a, h->d_tsdf_poses, s, h->tsdf_follow_on && b0 == 0 ? &fc : nullptr);
         HIPCHK(hipGetLastError());
         if (world_T_base) HIPCHK(hipStreamSynchronize(s));   // the staged host poses are reused
     }
@@ -551,7 +662,15 @@ int tslam_mesh_extract(tslam_handle* h, double min_weight, int64_t* n_tris, void
     if (!(min_weight >= 0.0)) return fail(TSLAM_EINVAL, "min_weight must be >= 0");
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = stream ? (hipStream_t)stream : h->last_stream;
-    const DenseArgs a = dense_args(h, min_weight);
+    DenseArgs a = dense_args(h, min_weight);
+    if (h->d_tsdf_win) {   // vertices in the tracking world: the window's corner as the device has it
+        int32_t sh[3];
+        double o[3];
+        if (const int rc = window_read(h, s, sh, o); rc != TSLAM_OK) return rc;
+        a.ox = o[0];
+        a.oy = o[1];
+        a.oz = o[2];
+    }
     h->mesh_n = 0;
     if (a.n_cubes == 0) {
         if (n_tris) *n_tris = 0;

@@ -300,9 +300,43 @@ struct TsdfArgs {
     const uint8_t* color;
     float* col;
     float* col_w;
+    // the rolling window's record (null: the volume's corner is ox, oy, oz as they stand; else the
+    // corner is o + s * (double)win->shift[a], thor_slam_amd/dense_follow.py)
+    const struct TsdfWindow* win;
+};
+// The rolling window (thor_slam_amd/dense_follow.py): the cumulative shift of the volume in whole
+// voxels, and the move the current call makes (delta; all zero: none).  Written on the device
+// (k_tsdf_follow, k_tsdf_shift), read by the move and by k_tsdf_integrate.
+struct TsdfWindow {
+    int32_t shift[3];
+    int32_t delta[3];
+};
+#define TSDF_SHIFT_LIMIT (1 << 30)   // |shift|, |delta| and the camera's voxel index stay below it
+struct TsdfFollow {
+    int32_t anchor[3];
+    int32_t margin, step;
+};
+// the layers of a volume as the move sees them: rows of nx * comp floats, ny * nz rows per layer
+struct TsdfLayers {
+    float* vol[4];
+    float* scratch[4];
+    int comp[4];
+    int n;
+    int nx, ny, nz;
+};
+// follow: the decision of an integrate call from the pose table of its first chunk (n entries);
+// shift: the same two fields from a caller's delta; move: the volume through the scratch and back
+void launch_tsdf_follow(const double* poses, int n, const TsdfArgs& a, const TsdfFollow& f, TsdfWindow* win, hipStream_t s);
+void launch_tsdf_shift(TsdfWindow* win, int dx, int dy, int dz, hipStream_t s);
+void launch_tsdf_move(const TsdfLayers& l, const TsdfWindow* win, hipStream_t s);
+// what a call's first chunk does between its poses and its integration when the window follows
+struct TsdfFollowCall {
+    TsdfFollow f;
+    TsdfLayers l;
+    TsdfWindow* win;
 };
 void launch_tsdf(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev, const TsdfArgs& a, double* poses,
-                 hipStream_t s);
+                 hipStream_t s, const TsdfFollowCall* follow = nullptr);
 // The rig's launch: every selected camera of every frame in one read-modify-write of the volume.
 // View v = f * n_cams + ci (frame-major, camera-minor) is integrated in ascending v, on the rig's
 // body pose: world_T_cam = (E_0^-1 T_abs(f)) E_pair.  TsdfArgs' n counts VIEWS here, and its depth /
@@ -322,7 +356,7 @@ struct TsdfRigArgs : TsdfArgs {
 // pairs: 8 bits per camera, camera ci's pair in bits 8 ci .. 8 ci + 7; f0: first frame within the batch
 // (device poses); host_wTb_dev: staged world_T_base [n_frames][16] or null
 void launch_tsdf_rig(const BatchCtx& c, uint64_t pairs, int f0, const double* host_wTb_dev, const TsdfRigArgs& a,
-                     double* poses, hipStream_t s);
+                     double* poses, hipStream_t s, const TsdfFollowCall* follow = nullptr);
 // dense stereo depth (k_stereo_depth.hip): n frames of one rectified pair -> disp32 (1/32 px) and
 // depth (mm), u16 [n][H][W]; win_left / win_right: u8 [n][H][W] winner maps between its two kernels
 struct StereoDepthArgs {

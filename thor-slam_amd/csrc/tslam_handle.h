@@ -241,6 +241,13 @@ struct tslam_handle {
     TsdfArgs tsdf{};
     double* d_tsdf_poses = nullptr;   // [TSDF_MAX_FRAMES][TSDF_POSE]
     double* d_tsdf_wTc = nullptr;     // [TSDF_MAX_FRAMES][16] host poses staged
+    // the rolling window (tslam_tsdf_follow / _shift): allocated on first use; once the record
+    // exists the volume's corner is the effective origin everywhere (TsdfArgs::win of every launch)
+    bool tsdf_follow_on = false;
+    TsdfFollow tsdf_follow{};
+    TsdfWindow* d_tsdf_win = nullptr; // {shift, delta}, written on the device
+    float* d_tsdf_scratch = nullptr;  // the move's copy of every layer (each layer's base a multiple of 4 floats)
+    size_t tsdf_scratch_cap = 0;
     // dense stereo depth (tslam_stereo_depth_*): parameters, output slots and winner-map scratch
     bool sd_on = false;
     tslam_stereo_depth_params sd_prm{};

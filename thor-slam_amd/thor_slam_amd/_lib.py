@@ -13,6 +13,7 @@ from pathlib import Path
 
 import numpy as np
 
+from .dense_follow import default_anchor
 from .params import HipSlamConfig
 
 LIB_NAME = "libtslam_hip.so"
@@ -115,6 +116,11 @@ class TsdfRigCamera(ctypes.Structure):
         ("pair", ctypes.c_int32), ("rect", ctypes.c_int32), ("depth", ctypes.c_void_p), ("color", ctypes.c_void_p),
         ("stride_bytes", ctypes.c_int64),
     ]
+
+
+class TsdfFollowParams(ctypes.Structure):
+    """tslam_tsdf_follow_params: the rolling window's rule (thor_slam_amd/dense_follow.py)."""
+    _fields_ = [("anchor", ctypes.c_int32 * 3), ("margin", ctypes.c_int32), ("step", ctypes.c_int32)]
 
 
 def camera_desc(cam) -> CameraDesc:
@@ -294,6 +300,9 @@ _SIGNATURES = {
                                                 ctypes.c_void_p, ctypes.c_void_p]),
     "tslam_stereo_depth_slots": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                                 ctypes.c_void_p]),
+    "tslam_tsdf_follow": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "tslam_tsdf_shift": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "tslam_tsdf_window": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 
@@ -854,6 +863,7 @@ class Handle:
         o = np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
         d = np.ascontiguousarray(dims, dtype=np.int32).reshape(3)
         self._tsdf_dims = tuple(int(x) for x in d)
+        self._tsdf_anchor = default_anchor(o, float(voxel_size))
         _check(self.lib.tslam_tsdf_init(self.h, o.ctypes.data, d.ctypes.data, float(voxel_size), float(trunc_vox),
                                         float(max_dist), float(max_weight)))
 
@@ -930,6 +940,32 @@ class Handle:
             poses = np.ascontiguousarray(np.asarray(world_T_base, dtype=np.float64).reshape(-1, 4, 4))
         _check(self.lib.tslam_tsdf_integrate_rig(self.h, ctypes.addressof(arr), len(cams), int(n_frames), int(first_frame),
                                                  None if poses is None else poses.ctypes.data, ctypes.c_void_p(stream)))
+
+    # -- the rolling window of the dense map (thor_slam_amd/dense_follow.py) ---------------------
+    def tsdf_follow(self, anchor=None, margin: int = 32, step: int = 16, enable: bool = True) -> None:
+        """The window follows the camera from the next integrate call on (``anchor`` None: the
+        voxel of the tracking world's origin in the unshifted window); ``enable`` False turns it
+        off and leaves the window where it is.  After ``tsdf_init``, which turns it off again."""
+        if not enable:
+            _check(self.lib.tslam_tsdf_follow(self.h, None))
+            return
+        if anchor is None:
+            anchor = getattr(self, "_tsdf_anchor", (0, 0, 0))   # without tsdf_init the library refuses the call
+        prm = TsdfFollowParams((ctypes.c_int32 * 3)(*[int(a) for a in anchor]), int(margin), int(step))
+        _check(self.lib.tslam_tsdf_follow(self.h, ctypes.addressof(prm)))
+
+    def tsdf_shift(self, delta, stream: int = 0) -> None:
+        """Move the window by ``delta`` voxels (x, y, z) on the stream; what leaves is dropped, what
+        enters is unobserved."""
+        d = np.ascontiguousarray(delta, dtype=np.int32).reshape(3)
+        _check(self.lib.tslam_tsdf_shift(self.h, d.ctypes.data, ctypes.c_void_p(stream)))
+
+    def tsdf_window(self) -> tuple[np.ndarray, np.ndarray]:
+        """(cumulative shift i32 [3] in voxels, effective origin f64 [3] in metres); synchronises."""
+        sh = np.zeros(3, dtype=np.int32)
+        o = np.zeros(3, dtype=np.float64)
+        _check(self.lib.tslam_tsdf_window(self.h, sh.ctypes.data, o.ctypes.data))
+        return sh, o
 
     # -- dense stereo depth (thor_slam_amd/stereo_depth.py) ------------------------------------
     def stereo_depth_init(self, max_frames: int = 1, n_disp: int = 0, uniqueness: int = 10, lr_tol: int = 1) -> None:

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 
+from .dense_follow import check_follow_params
 from .dense_rig import DenseCamerasError
 from .slam.interface import SlamConfig
 from .stereo_depth import check_params as check_stereo_depth_params
@@ -140,6 +141,16 @@ class HipSlamConfig(SlamConfig):
     # x right, y down, z forward): corner (m) and voxel counts (x, y, z); 10 x 4 x 11 m by default
     tsdf_origin: tuple = (-5.0, -2.0, -1.0)
     tsdf_dims: tuple = (200, 80, 220)
+    # the rolling window (thor_slam_amd/dense_follow.py): the volume keeps its size and follows the
+    # camera in whole voxels, decided on the device once per integrated batch: when the camera's
+    # voxel is more than dense_follow_margin voxels from dense_follow_anchor on an axis, the window
+    # moves by a multiple of dense_follow_step voxels (1 <= step <= margin); what leaves is dropped.
+    # Anchor None = the voxel of the tracking world's origin in the configured volume, so the layout
+    # of tsdf_origin / tsdf_dims around the camera is kept.  Needs dense_map and one device.
+    dense_follow: bool = False
+    dense_follow_margin: int = 32
+    dense_follow_step: int = 16
+    dense_follow_anchor: tuple | None = None
     # dense-map outputs (get_mesh / get_esdf / get_esdf_slice; thor_slam_amd/dense.py): nvblox's
     # mesh / ESDF integrator parameters (its defaults: min weight 1e-4, ESDF max distance 2 m, site
     # distance 1 voxel) and the 2-D slice's height band (y down: metres in the tracking world)
@@ -227,6 +238,13 @@ class HipSlamConfig(SlamConfig):
             if self.devices:
                 # rank 0 holds only its own cameras' records (and pair 0's pose, not the body's)
                 raise DenseCamerasError("dense_cameras does not run on a sharded rig (devices)")
+        if self.dense_follow:
+            if not self.dense_map:
+                raise ValueError("dense_follow needs dense_map=True")
+            if self.devices:
+                # the camera-sharded RGB-D map lives on rank 0, behind the shard driver
+                raise ValueError("dense_follow does not run on a sharded rig (devices)")
+            check_follow_params(self.dense_follow_margin, self.dense_follow_step, self.dense_follow_anchor)
         if not (self.ba_window == 0 or 2 <= self.ba_window <= 10):
             raise ValueError("ba_window must be 0 (off) or in [2, 10]")
         if self.ba_kf_interval < 1 or self.ba_iters < 1:

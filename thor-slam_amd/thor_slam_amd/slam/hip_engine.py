@@ -32,7 +32,10 @@ volume on the device with the batch's tracked poses (nvblox's role in the refere
 synchronous branch; ``get_depth_image`` returns the newest depth image.  ``dense_cameras`` ("all",
 or pair indices / source names) integrates those cameras of the rig instead, every frame of them
 in one launch per batch (``tslam_tsdf_integrate_rig``) on the rig's body poses, for RGB-D records
-and for dense stereo depth alike (``thor_slam_amd/dense_rig.py``).
+and for dense stereo depth alike (``thor_slam_amd/dense_rig.py``).  ``dense_follow`` lets the volume
+follow the camera in whole voxels, decided on the device once per integrated batch
+(``thor_slam_amd/dense_follow.py``); ``get_dense_map`` / ``get_esdf`` / ``get_esdf_slice`` then
+report the window's effective ``origin`` and its ``window_shift``.
 With ``HipSlamConfig(devices=[d0, d1, ...])`` the rig is sharded one camera stream per GPU from
 this one process (cuVSLAM's multicam mode, launch/thor_visual_slam.launch.py:49,81):
 one handle per device, driven by the library as one sharded rig (``tslam_group_*``: an RCCL clique
@@ -525,6 +528,8 @@ class HipSlamEngine(SlamEngine):
                 self._handle.tsdf_init(cfg.tsdf_origin, cfg.tsdf_dims, cfg.voxel_size,
                                        cfg.tsdf_integrator_truncation_distance_vox,
                                        cfg.tsdf_integrator_max_integration_distance_m, cfg.tsdf_max_weight)
+                if cfg.dense_follow:   # the window follows the camera (thor_slam_amd/dense_follow.py)
+                    self._handle.tsdf_follow(cfg.dense_follow_anchor, cfg.dense_follow_margin, cfg.dense_follow_step)
                 if cfg.stereo_depth:   # a stereo rig: the depth comes from the dense matcher (slots per camera)
                     self._handle.stereo_depth_init(max_frames=cfg.batch_size * max(1, len(self._dense_pairs)),
                                                    uniqueness=cfg.stereo_depth_uniqueness,
@@ -1015,7 +1020,8 @@ class HipSlamEngine(SlamEngine):
         """The TSDF volume (nvblox-shaped): ``tsdf`` / ``weight`` f32 [nz][ny][nx] (metres of
         truncated signed distance; weight 0 = never observed), the voxel grid (``origin``,
         ``voxel_size``, voxel (i, j, k) centred at origin + voxel_size (i, j, k) + voxel_size / 2 in
-        the tracking world) and ``world_T_volume`` (4x4: that frame in the published world =
+        the tracking world; with ``dense_follow`` the origin of the window as it stands, ``window_shift``
+        voxels from ``tsdf_origin``) and ``world_T_volume`` (4x4: that frame in the published world =
         base_link at the first frame).  None unless ``dense_map`` is on.  Synchronises."""
         cfg = self._config
         if not cfg.dense_map or self._handle is None:
@@ -1025,7 +1031,8 @@ class HipSlamEngine(SlamEngine):
         out = {}
         if self._dense_color:
             out["color"], out["color_weight"] = self._handle.tsdf_read_color()
-        return {**out, "tsdf": tsdf, "weight": weight, "origin": np.array(cfg.tsdf_origin, dtype=np.float64),
+        shift, origin = self._handle.tsdf_window()
+        return {**out, "tsdf": tsdf, "weight": weight, "origin": origin, "window_shift": shift,
                 "voxel_size": float(cfg.voxel_size),
                 "truncation_m": cfg.tsdf_integrator_truncation_distance_vox * cfg.voxel_size,
                 "world_T_volume": self._map_offset @ self._base_T_rect}
@@ -1054,7 +1061,8 @@ class HipSlamEngine(SlamEngine):
         self.flush()
         esdf = self._handle.esdf(cfg.esdf_integrator_max_distance_m, cfg.esdf_integrator_max_site_distance_vox,
                                  cfg.esdf_integrator_min_weight)
-        return {"esdf": esdf, "origin": np.array(cfg.tsdf_origin, dtype=np.float64), "voxel_size": float(cfg.voxel_size),
+        shift, origin = self._handle.tsdf_window()
+        return {"esdf": esdf, "origin": origin, "window_shift": shift, "voxel_size": float(cfg.voxel_size),
                 "world_T_volume": self._map_offset @ self._base_T_rect}
 
     def get_esdf_slice(self) -> dict | None:
@@ -1065,12 +1073,13 @@ class HipSlamEngine(SlamEngine):
         if not cfg.dense_map or self._handle is None:
             return None
         self.flush()
-        s, y_org, ny = cfg.voxel_size, cfg.tsdf_origin[1], int(cfg.tsdf_dims[1])
+        shift, origin = self._handle.tsdf_window()
+        s, y_org, ny = cfg.voxel_size, float(origin[1]), int(cfg.tsdf_dims[1])
         y0 = int(np.clip(np.floor((cfg.esdf_slice_min_height - y_org) / s), 0, ny - 1))
         y1 = int(np.clip(np.ceil((cfg.esdf_slice_max_height - y_org) / s), y0 + 1, ny))
         dist = self._handle.esdf_slice(y0, y1, cfg.esdf_integrator_max_distance_m,
                                        cfg.esdf_integrator_max_site_distance_vox, cfg.esdf_integrator_min_weight)
-        return {"distance": dist, "band": (y0, y1), "origin": np.array(cfg.tsdf_origin, dtype=np.float64),
+        return {"distance": dist, "band": (y0, y1), "origin": origin, "window_shift": shift,
                 "voxel_size": float(s), "world_T_volume": self._map_offset @ self._base_T_rect}
 
     def _read(self, n: int) -> dict:
