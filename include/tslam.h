@@ -612,6 +612,12 @@ int tslam_ba_graph(tslam_handle* h, int enable);
  * loop / relocalisation / map / TSDF calls, tslam_reset, tslam_destroy).  tslam_submit_host never
  * defers.  Results are identical; only the host's enqueue order changes. */
 int tslam_ba_defer(tslam_handle* h, int defer);
+/* Test hook for the top-K selection (results are identical on every path).  mode 0 (default): a
+ * level's candidates are kept in LDS after one read when they fit and a radix pass reads them
+ * again; 1: always the sweeps over global memory; 2: kept in LDS wherever they fit.  resident_cap
+ * 0 (default): each block shape's built-in capacity; N > 0: at most N candidates are kept resident
+ * (a level with more takes the global sweeps). */
+int tslam_select_mode(tslam_handle* h, int mode, int resident_cap);
 /* Measurement: `reps` back-to-back k_ba_schur launches on pair `pair`'s last solved window (the
  * kernel only rewrites its own outputs), between two HIP events on `stream`: the average launch
  * duration and the algorithmic flops per launch (for the FP64 MFMA roofline, without per-launch

@@ -879,18 +879,58 @@ __global__ __launch_bounds__(TS_DET_THREADS) void k_detect_fallback(BatchCtx c) 
 // ---------------------------------------------------------------------------------------------
 // A4 top-K: exact K_l smallest keys of an image level, sorted ascending.
 // Radix select on (score bin, y, x) histograms, then counting sorts (bitonic fallback) in LDS.
-// grid (n*C, n_levels), block 1024: blockIdx.y = level, so every level-0 block (the ~10k-
-// candidate sweeps) is dispatched in the first round and the short upper-level blocks follow;
-// LDS (42 KiB) and wave slots allow 2 such blocks per CU = 512 at once.
+//
+// The body is a template on the block's shape (SelShape): threads, counting-sort key capacity,
+// histogram bins and how many candidates it can keep resident in LDS.  The host picks the
+// smallest shape that holds a level (its quota, its width / height, its band count) and launches
+// one grid (n*C, levels of that shape) per shape, largest first:
+//   SelBig   1024 threads, 8192 keys (bitonic above 2048), 2048 bins   any level; the t + 1 fallback
+//   SelMid    512 threads, 2048 keys, 1024 bins                        a 640 x 400 level 0
+//   SelSmall  256 threads,  512 keys,  512 bins                        a few hundred keys
+//   SelWave    64 threads,  128 keys,  256 bins                        one wave: wave-level scans, and
+//                                                                      the barriers are no instructions
+// A 1024-thread block per level, whatever its size, had filled every wave slot of the CU with two
+// blocks that mostly sat in barriers (12,288 of a C2 launch's 16,384 blocks select <= 376 keys).
+//
+// Candidates are read from global memory once when they fit the shape's resident capacity: the
+// y-radix sweep (the first that needs the keys) also copies them into LDS, and the x-radix and
+// collect sweeps read LDS.  A level with more candidates than that (te = t + 1 on the first batch
+// and in the fallback, tie-heavy or noise images) sweeps global memory each time, as before.
 // ---------------------------------------------------------------------------------------------
 #define SEL_THREADS 1024
 #define SEL_MAX 8192
+#define TS_SEL_BUCKET_MAX 256   // larger score buckets -> bitonic fallback (O(n^2) ranking)
 
-// smallest bin b with sum(h[0..b]) >= need; returns b and the count strictly before it.
-// Inclusive scan of one value per thread over the block (SEL_THREADS = 16 waves): a 6-step
-// shuffle scan inside each wave, the 16 wave totals through LDS, two barriers in all (a
-// Hillis-Steele scan through LDS took 20).  s_w: 2 x 16 words, alternated by `phase` so that
-// back-to-back scans need no barrier between them.
+template <int NT_, int KCAP_, int BINS_, int RCAP_, bool BIG_>
+struct SelShape {
+    static constexpr int NT = NT_;       // threads per block (>= the level's bands)
+    static constexpr int KCAP = KCAP_;   // keys the counting sorts hold (>= the level's quota unless BIG)
+    static constexpr int BINS = BINS_;   // y / x / row bins (> the level's width and height)
+    static constexpr int RCAP = RCAP_;   // candidates resident in LDS (0: none)
+    static constexpr bool BIG = BIG_;    // 8192-key buffer with the bitonic path above KCAP keys
+    static constexpr int TMP = BIG_ ? SEL_MAX / 2 : KCAP_;                 // offsets in s_keys
+    static constexpr int FILL = BIG_ ? SEL_MAX / 2 + SEL_MAX / 4 : 2 * KCAP_;
+    static constexpr int KEYS = BIG_ ? SEL_MAX : 2 * KCAP_ + BINS_;
+};
+using SelBig = SelShape<1024, 2048, 2048, 8192, true>;
+using SelBigFallback = SelShape<1024, 2048, 2048, 0, true>;
+using SelMid = SelShape<512, 2048, 1024, 2560, false>;
+using SelSmall = SelShape<256, 512, 512, 1024, false>;
+using SelWave = SelShape<64, 128, 256, 256, false>;
+
+#define TS_SEL_MAX_CLASS_LEVELS TS_MAX_LEVELS
+struct SelArgs {
+    int nlev;                            // blockIdx.y -> level
+    int level[TS_SEL_MAX_CLASS_LEVELS];
+    int rcap;                            // resident capacity in force (<= RCAP; 0: always the global sweeps)
+    int eager;                           // 1: copy to LDS whenever it fits, not only when a radix pass needs the keys
+};
+
+// Inclusive scan of one value per thread over the block: a 6-step shuffle scan inside each wave,
+// the wave totals through LDS, two barriers in all (a Hillis-Steele scan through LDS took 20);
+// one wave needs neither.  s_w: 2 x 16 words, alternated by `phase` so that back-to-back scans
+// need no barrier between them.
+template <int NT>
 __device__ __forceinline__ uint32_t block_inclusive_scan(uint32_t v, uint32_t* s_w, int phase) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -898,6 +938,7 @@ __device__ __forceinline__ uint32_t block_inclusive_scan(uint32_t v, uint32_t* s
         const uint32_t t = (uint32_t)__shfl_up((int)v, o, 64);
         if (lane >= o) v += t;
     }
+    if constexpr (NT == 64) return v;
     uint32_t* w = s_w + 16 * (phase & 1);
     if (lane == 63) w[wave] = v;
     __syncthreads();
@@ -906,37 +947,43 @@ __device__ __forceinline__ uint32_t block_inclusive_scan(uint32_t v, uint32_t* s
     return v + add;
 }
 
-__device__ void block_find_crossing(const uint32_t* h, int nbins, uint32_t need, uint32_t* s_part,
-                                    int* out_bin, uint32_t* out_before) {
-    const int per = (nbins + SEL_THREADS - 1) / SEL_THREADS;
+// smallest bin b with sum(h[0..b]) >= need: its index, the count strictly before it and its own
+// count; also the sum of all bins (the scan has it).  Ends synchronised, and nothing reads h
+// after that barrier, so the caller may overwrite h at once.
+template <int NT>
+__device__ __forceinline__ void block_find_crossing(const uint32_t* h, int nbins, uint32_t need, uint32_t* s_part,
+                                                    uint32_t* out /* bin, before, eq, total */) {
+    const int per = (nbins + NT - 1) / NT;
     const int b0 = threadIdx.x * per;
     uint32_t local = 0;
     for (int b = b0; b < min(b0 + per, nbins); ++b) local += h[b];
-    const uint32_t incl = block_inclusive_scan(local, s_part, 0);
+    const uint32_t incl = block_inclusive_scan<NT>(local, s_part, 0);
     const uint32_t excl = incl - local;
+    if (threadIdx.x == NT - 1) out[3] = incl;
     if (excl < need && incl >= need) {
         uint32_t cum = excl;
         for (int b = b0; b < min(b0 + per, nbins); ++b) {
-            if (cum + h[b] >= need) {
-                *out_bin = b;
-                *out_before = cum;
+            const uint32_t v = h[b];
+            if (cum + v >= need) {
+                out[0] = (uint32_t)b;
+                out[1] = cum;
+                out[2] = v;
                 break;
             }
-            cum += h[b];
+            cum += v;
         }
     }
     __syncthreads();
 }
 
-#define TS_SEL_BUCKET_MAX 256   // larger score buckets -> bitonic fallback (O(n^2) ranking)
-
-// In-place exclusive scan of a[0..n) (n <= 8 * SEL_THREADS) by the whole block; ends synchronised.
-__device__ void block_exclusive_scan(uint32_t* a, int n, uint32_t* s_part) {
-    const int per = (n + SEL_THREADS - 1) / SEL_THREADS;
+// In-place exclusive scan of a[0..n) by the whole block; ends synchronised.
+template <int NT>
+__device__ __forceinline__ void block_exclusive_scan(uint32_t* a, int n, uint32_t* s_part) {
+    const int per = (n + NT - 1) / NT;
     const int b0 = threadIdx.x * per;
     uint32_t local = 0;
     for (int b = b0; b < min(b0 + per, n); ++b) local += a[b];
-    uint32_t run = block_inclusive_scan(local, s_part, 1) - local;
+    uint32_t run = block_inclusive_scan<NT>(local, s_part, 1) - local;
     for (int b = b0; b < min(b0 + per, n); ++b) {
         const uint32_t v = a[b];
         a[b] = run;
@@ -945,15 +992,17 @@ __device__ void block_exclusive_scan(uint32_t* a, int n, uint32_t* s_part) {
     __syncthreads();
 }
 
-// Ascending bitonic sort of a[0..n) in place (pads to a power of two with 0xFFFFFFFF; n <= SEL_MAX).
-__device__ void bitonic_sort(uint32_t* a, int n) {
+// Ascending bitonic sort of a[0..n) in place (pads to a power of two with 0xFFFFFFFF; the buffer
+// holds that power of two).
+template <int NT>
+__device__ __forceinline__ void bitonic_sort(uint32_t* a, int n) {
     int np2 = 1;
     while (np2 < n) np2 <<= 1;
-    for (int i = n + threadIdx.x; i < np2; i += SEL_THREADS) a[i] = 0xFFFFFFFFu;
+    for (int i = n + threadIdx.x; i < np2; i += NT) a[i] = 0xFFFFFFFFu;
     __syncthreads();
     for (int k = 2; k <= np2; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < np2; i += SEL_THREADS) {
+            for (int i = threadIdx.x; i < np2; i += NT) {
                 const int p = i ^ j;
                 if (p > i) {
                     const uint32_t x = a[i], y = a[p];
@@ -969,14 +1018,23 @@ __device__ void bitonic_sort(uint32_t* a, int n) {
     }
 }
 
-template <int MODE>
-__device__ __forceinline__ void select_body(const BatchCtx& c, int img, int l) {
-    __shared__ uint32_t s_keys[SEL_MAX];
-    __shared__ uint32_t s_h[2048];
-    __shared__ uint32_t s_part[SEL_THREADS];
-    __shared__ uint32_t s_pref[SEL_THREADS + 1];
-    __shared__ int s_bin;
-    __shared__ uint32_t s_before, s_nsel, s_flag;
+// LDS of one block: s_keys = keys | s_tmp | s_fill (SelShape::TMP / FILL), s_a and s_fill are the
+// y and x radix histograms first and the row counts and row fill counters of the y-order later
+// (zero whenever a pass that counts into them starts), s_h the score histogram, then the score
+// buckets [0, 256) and their fill counters [256, 512).
+template <int MODE, typename S>
+__device__ __forceinline__ void select_body(const BatchCtx& c, int img, int l, int rcap, int eager) {
+    constexpr int NT = S::NT, BINS = S::BINS;
+    __shared__ uint32_t s_keys[S::KEYS];
+    __shared__ uint32_t s_a[BINS];
+    __shared__ uint32_t s_h[512];
+    __shared__ uint32_t s_res[S::RCAP > 0 ? S::RCAP : 1];
+    __shared__ uint32_t s_part[32];
+    __shared__ uint32_t s_pref[NT + 1];
+    __shared__ uint32_t s_x[4];   // block_find_crossing: bin, before, eq, total
+    __shared__ uint32_t s_nsel, s_flag;
+    uint32_t* const s_tmp = s_keys + S::TMP;
+    uint32_t* const s_fill = s_keys + S::FILL;
     int f, cam;
     view_image(c, img, &f, &cam);
     const size_t fcl = ((size_t)f * c.C + cam) * c.g.n_levels + l;
@@ -990,30 +1048,39 @@ __device__ __forceinline__ void select_body(const BatchCtx& c, int img, int l) {
     // band counts -> exclusive prefix (flat candidate index i lives in band b with
     // s_pref[b] <= i < s_pref[b+1]); every pass below is then one flat, independent-load sweep
     // over the level's candidates (a per-band loop serialised ~25 dependent global round trips)
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) {
+    for (int i = threadIdx.x; i < 256; i += NT) {
         s_h[i] = gh[i];
+        s_h[256 + i] = 0u;
         gh[i] = 0u;   // back to zero for the next detect of this image-level (fallback or next batch)
+    }
+    for (int i = threadIdx.x; i < BINS; i += NT) {
+        s_a[i] = 0u;
+        s_fill[i] = 0u;
+    }
+    if (threadIdx.x == 0) {
+        s_nsel = 0;
+        s_flag = 0;
     }
     {
         const uint32_t bc = (int)threadIdx.x < nb ? cnt[threadIdx.x] : 0u;
-        const uint32_t incl = block_inclusive_scan(bc, s_part, 1);
+        const uint32_t incl = block_inclusive_scan<NT>(bc, s_part, 1);
         if (threadIdx.x == 0) s_pref[0] = 0u;
         if ((int)threadIdx.x < nb) s_pref[threadIdx.x + 1] = incl;
     }
     __syncthreads();
     const int ncand = (int)s_pref[nb];
-    // sweep(fn): fn(key) for every candidate, 4 independent loads in flight per thread.  A
+    // sweep_g(fn): fn(i, key) for every candidate, 4 independent loads in flight per thread.  A
     // thread's indices only grow along a sweep, so its band (the b with s_pref[b] <= i <
     // s_pref[b+1]; s_pref[nb] = ncand ends the walk) is found by walking forward from the
     // previous candidate's band (no per-candidate search); band * cap < 2^21 (W, H <= 2047, tslam_create), so the address
     // is a full-rate 24-bit multiply
-    auto sweep = [&](auto&& fn) {
+    auto sweep_g = [&](auto&& fn) {
         int lo = 0;
-        for (int i0 = threadIdx.x; i0 < ncand; i0 += 4 * SEL_THREADS) {
+        for (int i0 = threadIdx.x; i0 < ncand; i0 += 4 * NT) {
             uint32_t k[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const int i = i0 + u * SEL_THREADS;
+                const int i = i0 + u * NT;
                 k[u] = 0u;
                 if (i < ncand) {
                     while ((int)s_pref[lo + 1] <= i) ++lo;
@@ -1022,53 +1089,70 @@ __device__ __forceinline__ void select_body(const BatchCtx& c, int img, int l) {
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u)
-                if (i0 + u * SEL_THREADS < ncand) fn(k[u]);
+                if (i0 + u * NT < ncand) fn(i0 + u * NT, k[u]);
         }
     };
-    uint32_t total = 0;
-    for (int i = 0; i < 256; ++i) total += s_h[i];   // uniform per thread (LDS broadcast)
+    // The resident copy: candidate i sits in s_res[i].  Every sweep gives thread t the indices
+    // t, t + NT, ..., so a thread reads back only what it stored itself.
+    bool res = false;   // block-uniform
+    auto sweep = [&](auto&& fn) {
+        if (S::RCAP > 0 && res) {
+            for (int i = threadIdx.x; i < ncand; i += NT) fn(i, s_res[i]);
+        } else {
+            sweep_g(fn);
+        }
+    };
+    const bool fits = S::RCAP > 0 && ncand <= rcap;
 
+    // the score bin of the K-th key; the scan behind it also gives the level's candidate total
+    block_find_crossing<NT>(s_h, 256, (uint32_t)Kl, s_part, s_x);
+    const uint32_t total = s_x[3];
+    for (int i = threadIdx.x; i < 256; i += NT) s_h[i] = 0u;   // the score buckets of the sort below
     uint32_t thresh = 0xFFFFFFFFu;  // inclusive max key taken
     if (total > (uint32_t)Kl) {
-        block_find_crossing(s_h, 256, (uint32_t)Kl, s_part, &s_bin, &s_before);
-        const uint32_t sbin = (uint32_t)s_bin;  // = 255 - s*
-        const uint32_t need = (uint32_t)Kl - s_before;
-        const uint32_t eq = s_h[sbin];
+        const uint32_t sbin = s_x[0];  // = 255 - s*
+        const uint32_t need = (uint32_t)Kl - s_x[1];
+        const uint32_t eq = s_x[2];
         thresh = (sbin << 22) | 0x3FFFFFu;
         if (need < eq) {
-            // radix on y among keys of this score
-            __syncthreads();
-            for (int i = threadIdx.x; i < 2048; i += blockDim.x) s_h[i] = 0;
-            __syncthreads();
-            sweep([&](uint32_t k) {
-                if ((k >> 22) == sbin) atomicAdd(&s_h[(k >> 11) & 2047u], 1u);
+            // radix on y among keys of this score; the one read of global memory when the keys fit
+            res = fits;
+            sweep_g([&](int i, uint32_t k) {
+                if (S::RCAP > 0 && res) s_res[i] = k;
+                if ((k >> 22) == sbin) atomicAdd(&s_a[(k >> 11) & 2047u], 1u);
             });
             __syncthreads();
-            block_find_crossing(s_h, 2048, need, s_part, &s_bin, &s_before);
-            const uint32_t ystar = (uint32_t)s_bin;
-            const uint32_t need2 = need - s_before;
-            const uint32_t eq2 = s_h[ystar];
+            block_find_crossing<NT>(s_a, BINS, need, s_part, s_x);
+            const uint32_t ystar = s_x[0];
+            const uint32_t need2 = need - s_x[1];
+            const uint32_t eq2 = s_x[2];
             thresh = (sbin << 22) | (ystar << 11) | 2047u;
+            for (int i = threadIdx.x; i < BINS; i += NT) s_a[i] = 0u;   // the row counts below
             if (need2 < eq2) {
-                __syncthreads();
-                for (int i = threadIdx.x; i < 2048; i += blockDim.x) s_h[i] = 0;
-                __syncthreads();
-                sweep([&](uint32_t k) {
-                    if ((k >> 11) == ((sbin << 11) | ystar)) atomicAdd(&s_h[k & 2047u], 1u);
+                sweep([&](int, uint32_t k) {
+                    if ((k >> 11) == ((sbin << 11) | ystar)) atomicAdd(&s_fill[k & 2047u], 1u);
                 });
                 __syncthreads();
-                block_find_crossing(s_h, 2048, need2, s_part, &s_bin, &s_before);
-                thresh = (sbin << 22) | (ystar << 11) | (uint32_t)s_bin;
+                block_find_crossing<NT>(s_fill, BINS, need2, s_part, s_x);
+                thresh = (sbin << 22) | (ystar << 11) | s_x[0];
+                // the row fill counters below.  Not where the quota exceeds the counting sorts'
+                // capacity (BIG only): the x radix ran, so nsel = Kl takes the bitonic path, which
+                // has no row fill, and the collect of a faster wave may already be writing keys
+                // into s_keys[FILL..) (no barrier lies between; Kl <= KCAP keeps the slots below TMP)
+                if (!S::BIG || Kl <= S::KCAP)
+                    for (int i = threadIdx.x; i < BINS; i += NT) s_fill[i] = 0u;
             }
         }
     }
-    // collect survivors
-    if (threadIdx.x == 0) s_nsel = 0;
-    __syncthreads();
-    sweep([&](uint32_t k) {
+    if (S::RCAP > 0 && !res && fits && eager) {
+        sweep_g([&](int i, uint32_t k) { s_res[i] = k; });
+        res = true;
+    }
+    // collect survivors (s_nsel is zero since the top; the barriers of the crossing lie between)
+    sweep([&](int, uint32_t k) {
         if (k <= thresh) {
             const uint32_t slot = atomicAdd(&s_nsel, 1u);
-            if (slot < SEL_MAX) s_keys[slot] = k;
+            if (slot < (uint32_t)(S::BIG ? SEL_MAX : S::KCAP)) s_keys[slot] = k;
         }
     });
     __syncthreads();
@@ -1076,29 +1160,27 @@ __device__ __forceinline__ void select_body(const BatchCtx& c, int img, int l) {
     const int slot = ring_slot(c, c.g0 + f);
     uint32_t* kp = c.kps + (((size_t)slot * c.C + cam) * c.g.K + c.g.koff[l]) * 2;
     const int Hl = c.g.H[l];
-    // Counting sorts (few barriers) when the level fits a quarter of s_keys and no score
-    // bucket is huge; a bitonic network otherwise (66 barrier stages at 2048 keys).  Keys are
-    // unique, so "rank = bucket offset + #smaller keys in the bucket" is the sorted position.
-    uint32_t* s_tmp = s_keys + SEL_MAX / 2;
-    if (threadIdx.x == 0) s_flag = 0;
-    for (int i = threadIdx.x; i < 512; i += SEL_THREADS) s_h[i] = 0;
-    __syncthreads();
-    const bool counting = nsel <= SEL_MAX / 4;   // s_tmp = [4096, 6144), row fill = [6144, 8192)
+    // Counting sorts (few barriers) when the level fits s_tmp (always, unless the shape is BIG)
+    // and no score bucket is huge; a bitonic network otherwise (66 barrier stages at 2048 keys).
+    // Keys are unique, so "rank = bucket offset + #smaller keys in the bucket" is the sorted
+    // position.  s_h[0, 512) and s_flag are zero here (zeroed above, barriers since).
+    const bool counting = !S::BIG || nsel <= S::KCAP;
     if (counting) {
-        for (int i = threadIdx.x; i < nsel; i += SEL_THREADS) atomicAdd(&s_h[s_keys[i] >> 22], 1u);
+        for (int i = threadIdx.x; i < nsel; i += NT) atomicAdd(&s_h[s_keys[i] >> 22], 1u);
         __syncthreads();
-        if (threadIdx.x < 256 && s_h[threadIdx.x] > TS_SEL_BUCKET_MAX) s_flag = 1;   // one score bucket per thread
-        block_exclusive_scan(s_h, 256, s_part);      // s_h[b] = bucket offset
+        for (int b = threadIdx.x; b < 256; b += NT)
+            if (s_h[b] > TS_SEL_BUCKET_MAX) s_flag = 1;
+        block_exclusive_scan<NT>(s_h, 256, s_part);      // s_h[b] = bucket offset
     }
     __syncthreads();
     if (counting && s_flag == 0) {
         uint32_t* fill = s_h + 256;
-        for (int i = threadIdx.x; i < nsel; i += SEL_THREADS) {
+        for (int i = threadIdx.x; i < nsel; i += NT) {
             const uint32_t k = s_keys[i], b = k >> 22;
             s_tmp[s_h[b] + atomicAdd(&fill[b], 1u)] = k;
         }
         __syncthreads();
-        for (int i = threadIdx.x; i < nsel; i += SEL_THREADS) {
+        for (int i = threadIdx.x; i < nsel; i += NT) {
             const uint32_t k = s_tmp[i], b = k >> 22;
             const int lo = (int)s_h[b], n = (int)fill[b];
             int r = 0;
@@ -1107,9 +1189,9 @@ __device__ __forceinline__ void select_body(const BatchCtx& c, int img, int l) {
         }
         __syncthreads();
     } else {
-        bitonic_sort(s_keys, nsel);
+        bitonic_sort<NT>(s_keys, nsel);
     }
-    for (int i = threadIdx.x; i < Kl; i += SEL_THREADS) {
+    for (int i = threadIdx.x; i < Kl; i += NT) {
         uint32_t xy = 0, meta = (uint32_t)l;   // padding entries keep their level
         if (i < nsel) {
             const uint32_t k = s_keys[i];
@@ -1149,28 +1231,23 @@ __device__ __forceinline__ void select_body(const BatchCtx& c, int img, int l) {
         return {(k & 2047u) | (((k >> 11) & 2047u) << 16), (uint32_t)l | ((255u - (k >> 22)) << 16),
                 (uint32_t)(c.g.koff[l] + rank), 1u};
     };
-    for (int i = nsel + threadIdx.x; i < Kl; i += SEL_THREADS) ys[i] = {0u, (uint32_t)l, (uint32_t)(c.g.koff[l] + i), 0u};
+    for (int i = nsel + threadIdx.x; i < Kl; i += NT) ys[i] = {0u, (uint32_t)l, (uint32_t)(c.g.koff[l] + i), 0u};
     if (counting) {
         // rows: counts -> exclusive offsets (= rowstart), bucket ranks by row, order by rank
-        uint32_t* fill = s_keys + SEL_MAX / 2 + SEL_MAX / 4;   // [2048] row fill counters
+        // (s_a and s_fill are zero: zeroed at the top or after the radix pass that used them,
+        // with the barrier after the collect since; the sort above ended on a barrier)
+        for (int i = threadIdx.x; i < nsel; i += NT) atomicAdd(&s_a[(s_keys[i] >> 11) & 2047u], 1u);
         __syncthreads();
-        for (int i = threadIdx.x; i < 2048; i += SEL_THREADS) {
-            s_h[i] = 0;
-            fill[i] = 0;
-        }
-        __syncthreads();
-        for (int i = threadIdx.x; i < nsel; i += SEL_THREADS) atomicAdd(&s_h[(s_keys[i] >> 11) & 2047u], 1u);
-        __syncthreads();
-        block_exclusive_scan(s_h, 2048, s_part);
-        for (int y = threadIdx.x; y <= Hl; y += SEL_THREADS) rs[y] = (uint16_t)s_h[y];
-        for (int i = threadIdx.x; i < nsel; i += SEL_THREADS) {
+        block_exclusive_scan<NT>(s_a, BINS, s_part);
+        for (int y = threadIdx.x; y <= Hl; y += NT) rs[y] = (uint16_t)s_a[y];
+        for (int i = threadIdx.x; i < nsel; i += NT) {
             const uint32_t y = (s_keys[i] >> 11) & 2047u;
-            s_tmp[s_h[y] + atomicAdd(&fill[y], 1u)] = (uint32_t)i;
+            s_tmp[s_a[y] + atomicAdd(&s_fill[y], 1u)] = (uint32_t)i;
         }
         __syncthreads();
-        for (int p = threadIdx.x; p < nsel; p += SEL_THREADS) {
+        for (int p = threadIdx.x; p < nsel; p += NT) {
             const uint32_t i = s_tmp[p], y = (s_keys[i] >> 11) & 2047u;
-            const int lo = (int)s_h[y], n = (int)fill[y];
+            const int lo = (int)s_a[y], n = (int)s_fill[y];
             int r = 0;
             for (int j = lo; j < lo + n; ++j) r += s_tmp[j] < i;
             ys[lo + r] = record((int)i);
@@ -1180,15 +1257,15 @@ __device__ __forceinline__ void select_body(const BatchCtx& c, int img, int l) {
         // sort in place after the records are taken
         __syncthreads();
         uint32_t* yk = s_keys;   // reuse: keys are re-derived from kp[] below
-        for (int i = threadIdx.x; i < nsel; i += SEL_THREADS) yk[i] = (((yk[i] >> 11) & 2047u) << 13) | (uint32_t)i;
+        for (int i = threadIdx.x; i < nsel; i += NT) yk[i] = (((yk[i] >> 11) & 2047u) << 13) | (uint32_t)i;
         __syncthreads();
-        bitonic_sort(yk, nsel);
-        for (int i = threadIdx.x; i < nsel; i += SEL_THREADS) {
+        bitonic_sort<NT>(yk, nsel);
+        for (int i = threadIdx.x; i < nsel; i += NT) {
             const int rank = (int)(yk[i] & 8191u);
             const uint2 e = *reinterpret_cast<const uint2*>(kp + 2 * rank);
             ys[i] = {e.x, e.y, (uint32_t)(c.g.koff[l] + rank), 1u};
         }
-        for (int y = threadIdx.x; y <= Hl; y += SEL_THREADS) {
+        for (int y = threadIdx.x; y <= Hl; y += NT) {
             const uint32_t target = (uint32_t)y << 13;
             int lo = 0, hi = nsel;  // first position with key >= target
             while (lo < hi) {
@@ -1200,9 +1277,15 @@ __device__ __forceinline__ void select_body(const BatchCtx& c, int img, int l) {
     }
 }
 
-__global__ __launch_bounds__(SEL_THREADS) void k_select(BatchCtx c) { select_body<0>(c, blockIdx.x, blockIdx.y); }
+// One kernel per shape, grid (n*C, levels of that shape); separate launches, because the block
+// size is a property of the launch and a one-wave block is the point of SelWave.
+template <typename S>
+__global__ __launch_bounds__(S::NT) void k_select(BatchCtx c, SelArgs a) {
+    select_body<0, S>(c, blockIdx.x, a.level[blockIdx.y], a.rcap, a.eager);
+}
+// at t + 1 every level has far more candidates than any resident capacity: no resident buffer
 __global__ __launch_bounds__(SEL_THREADS) void k_select_fallback(BatchCtx c) {
-    for_flagged_levels(c, SEL_THREADS, [&](int img, int l) { select_body<1>(c, img, l); });
+    for_flagged_levels(c, SEL_THREADS, [&](int img, int l) { select_body<1, SelBigFallback>(c, img, l, 0, 0); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1233,9 +1316,35 @@ __global__ void k_det_thr_commit(BatchCtx c) {
     c.det_thr_acc[k] = 0xFFFFFFFFu;
 }
 
-void launch_select(const BatchCtx& c, hipStream_t s) {
-    dim3 grid(c.n * c.ncam, c.g.n_levels);
-    hipLaunchKernelGGL(k_select, grid, dim3(SEL_THREADS), 0, s, c);
+template <typename S>
+static bool select_shape_holds(const LevelGeom& g, int l) {
+    return g.Kq[l] <= S::KCAP && g.W[l] <= S::BINS && g.H[l] < S::BINS && g.nbands[l] <= S::NT;
+}
+
+// one launch for the levels whose smallest holding shape is S (shape_of[l] == id)
+template <typename S>
+static void launch_select_shape(const BatchCtx& c, hipStream_t s, int mode, int rcap, const int* shape_of, int id) {
+    SelArgs a{};
+    for (int l = 0; l < c.g.n_levels; ++l)
+        if (shape_of[l] == id) a.level[a.nlev++] = l;
+    if (a.nlev == 0) return;
+    a.rcap = mode == 1 ? 0 : (rcap > 0 ? std::min(rcap, (int)S::RCAP) : (int)S::RCAP);
+    a.eager = mode == 2;
+    hipLaunchKernelGGL(k_select<S>, dim3(c.n * c.ncam, a.nlev), dim3(S::NT), 0, s, c, a);
+}
+
+// mode 0: resident when the candidates fit and a radix pass reads them again; 1: never; 2: whenever
+// they fit.  rcap > 0 lowers every shape's resident capacity to at most rcap candidates.
+void launch_select(const BatchCtx& c, hipStream_t s, int mode, int rcap) {
+    int shape_of[TS_MAX_LEVELS];
+    for (int l = 0; l < c.g.n_levels; ++l)
+        shape_of[l] = select_shape_holds<SelWave>(c.g, l) ? 0 : select_shape_holds<SelSmall>(c.g, l) ? 1
+                      : select_shape_holds<SelMid>(c.g, l) ? 2 : 3;
+    // the largest shape first: its blocks live longest, and the small ones fill in behind them
+    launch_select_shape<SelBig>(c, s, mode, rcap, shape_of, 3);
+    launch_select_shape<SelMid>(c, s, mode, rcap, shape_of, 2);
+    launch_select_shape<SelSmall>(c, s, mode, rcap, shape_of, 1);
+    launch_select_shape<SelWave>(c, s, mode, rcap, shape_of, 0);
     // fallback for images whose speculative threshold left fewer than K candidates: detect and
     // select again at t + 1, gated on the device flags (near-empty launches when none is set)
     hipLaunchKernelGGL(k_detect_fallback, dim3(TS_FB_BLOCKS), dim3(TS_DET_THREADS), (size_t)c.g.det_lds, s, c);

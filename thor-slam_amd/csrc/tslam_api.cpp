@@ -239,9 +239,9 @@ int run_front_stage(tslam_handle* h, const BatchCtx& c, int stage, hipStream_t s
             if (h->prm.rgbd) launch_rgbd_gray(c, h->d_gray, s);   // the colour images become the gray input of rectify
             launch_rectify_pyramid(c, s);
             return 1;
-        case TSLAM_STAGE_DETECT: launch_detect(c, s); launch_select(c, s); return 1;
+        case TSLAM_STAGE_DETECT: launch_detect(c, s); launch_select(c, s, h->sel_mode, h->sel_rcap); return 1;
         case TSLAM_KERNEL_DETECT: launch_detect(c, s); return 1;
-        case TSLAM_KERNEL_SELECT: launch_select(c, s); return 1;
+        case TSLAM_KERNEL_SELECT: launch_select(c, s, h->sel_mode, h->sel_rcap); return 1;
         case TSLAM_STAGE_DESCRIBE:
         case TSLAM_KERNEL_DESCRIBE: launch_describe(c, s); return 1;
         default: return 0;
@@ -859,6 +859,13 @@ int tslam_read_poses(tslam_handle* h, int max_frames, double* T_rel, double* T_a
     if (rc != TSLAM_OK) return rc;
     return copy_pose_records((const double*)h->buf[TSLAM_BUF_POSE].ptr, (const int32_t*)h->buf[TSLAM_BUF_STATS].ptr,
                              h->cur_n * h->P, T_rel, T_abs, cov, stats);
+}
+
+int tslam_select_mode(tslam_handle* h, int mode, int resident_cap) {
+    if (!h || mode < 0 || mode > 2 || resident_cap < 0) return fail(TSLAM_EINVAL, "bad handle, select mode or capacity");
+    h->sel_mode = mode;
+    h->sel_rcap = resident_cap;
+    return TSLAM_OK;
 }
 
 int tslam_buffer_info(tslam_handle* h, int which, void** device_ptr, int64_t* bytes_total, int64_t* bytes_per_frame) {

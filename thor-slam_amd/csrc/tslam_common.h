@@ -199,7 +199,7 @@ __device__ __forceinline__ size_t view_src(const BatchCtx& c, int img) {
 // host launchers (one per stage kernel set)
 void launch_rectify_pyramid(const BatchCtx& c, hipStream_t s);
 void launch_detect(const BatchCtx& c, hipStream_t s);
-void launch_select(const BatchCtx& c, hipStream_t s);
+void launch_select(const BatchCtx& c, hipStream_t s, int mode, int rcap);   // tslam_select_mode
 void launch_describe(const BatchCtx& c, hipStream_t s);
 void launch_match(const BatchCtx& c, hipStream_t s);
 void launch_match_refine(const BatchCtx& c, hipStream_t s);

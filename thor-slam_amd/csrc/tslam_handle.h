@@ -115,6 +115,9 @@ struct tslam_handle {
     // stage, or any call that reads or changes BA state), so the caller's next front stages are on
     // the GPU before this batch's ~160 BA launches are issued from the host
     bool ba_defer = false;
+    // tslam_select_mode: the path of k_select (0 auto, 1 global sweeps, 2 resident wherever it fits)
+    // and a cap on the candidates kept resident (0: each block shape's own capacity)
+    int sel_mode = 0, sel_rcap = 0;
     struct {
         bool pending = false;
         BatchCtx c{};

@@ -233,6 +233,7 @@ _SIGNATURES = {
                                               ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "tslam_ba_split_solve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "tslam_ba_defer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "tslam_select_mode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
     "tslam_ba_inertial": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
                                          ctypes.c_void_p, ctypes.c_double]),
     "tslam_ba_inertial_factor": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p,
@@ -360,6 +361,7 @@ def _check(rc: int) -> None:
 
 RANSAC_MODE = {"auto": 0, "exhaustive": 1, "bounded": 2}   # tslam_params.ransac_mode
 MATCH_REFINE = {"auto": 0, "split": 1}   # tslam_params.match_refine
+SELECT_MODE = {"auto": 0, "generic": 1, "resident": 2}   # tslam_select_mode
 
 
 def make_params(cfg: HipSlamConfig, max_batch: int, n_pairs: int, ransac_splits: int = 0,
@@ -1119,6 +1121,11 @@ class Handle:
         """``tslam_ba_defer``: a BA stage on its own stream is enqueued at the next flush point
         (the next batch's first back stage, or any state read) instead of inside the stage call."""
         _check(self.lib.tslam_ba_defer(self.h, int(bool(defer))))
+
+    def select_mode(self, mode: str = "auto", resident_cap: int = 0) -> None:
+        """``tslam_select_mode`` (test hook): the top-K selection's path, ``auto`` / ``generic`` (global
+        sweeps) / ``resident`` (LDS wherever it fits), and a cap on the resident candidates (0: built in)."""
+        _check(self.lib.tslam_select_mode(self.h, SELECT_MODE[mode], int(resident_cap)))
 
     def ba_graph(self, enable: bool) -> None:
         """Pair windows' keyframe chains from captured hipGraphs (default) or direct launches (tslam.h)."""
