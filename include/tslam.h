@@ -906,6 +906,53 @@ int tslam_tsdf_follow(tslam_handle* h, const tslam_tsdf_follow_params* params);
 int tslam_tsdf_shift(tslam_handle* h, const int32_t* delta, void* stream);
 int tslam_tsdf_window(tslam_handle* h, int32_t* shift, double* origin);
 
+/* The dense map seen from a pose: TSDF ray casting (added within ABI 21: four new symbols and a
+ * struct; nothing else changes, and a handle that calls none of them behaves as before).  Spec:
+ * thor_slam_amd/dense_render.py.  For every pixel of an undistorted pinhole camera at world_T_cam
+ * (in the volume's frame) the surface the volume holds: depth along the camera's z axis, the
+ * normal in the volume's frame (pointing into free space) and the nearest voxel's colour.  A pixel
+ * whose ray finds no surface, and every pixel of an unused view, is zero in every output.
+ *
+ * tslam_tsdf_render_init: the camera, the marching parameters, the outputs wanted (a bit mask of
+ *   TSLAM_RENDER_*) and the most views of one call (1..256).  Builds the camera's ray-length table
+ *   and sizes the handle's images.  TSLAM_ESTATE without a volume or inside a batch; TSLAM_EINVAL
+ *   unless the volume has dims >= 2, 1 <= width, height <= 16384, fx, fy > 0, min_weight >= 0,
+ *   0 <= min_depth < max_depth, 0 < step_scale <= 1 (all finite), outputs in 1..15 and reserved 0.
+ *   Calling it again replaces the state.  tslam_reset keeps the state and clears the images.
+ * tslam_tsdf_render: n_views (0..max_views) views into image slots 0.., on `stream` (NULL: the
+ *   handle's last stream); the call does not wait for the images.  world_T_cam: [n_views][16] on the
+ *   host, row-major, copied to the device by an asynchronous copy from the caller's (pageable)
+ *   memory: the runtime reads it before the call returns, and may make the host wait for the
+ *   stream's earlier work to do so.  The device-pose path (NULL) never waits.  A pose whose first
+ *   element is not finite gives a zero image.  NULL: frames first_frame.. of the last batch (they must belong to it) with
+ *   `pair`'s device-resident chained poses, untracked frames giving zero images.  The volume is
+ *   read as the stream finds it (after earlier integrate and shift calls on it); calls on
+ *   different streams share the images and the staged poses and are the caller's to order.
+ * tslam_tsdf_render_buffers: the device pointers (NULL for an output not asked for) and, in
+ *   view_bytes[4], the bytes of one view of depth_m (f32 [H][W], metres), depth_mm (u16 [H][W], the
+ *   format tslam_tsdf_integrate reads), normal (f32 [H][W][3]) and color (u8 [H][W][3], B, G, R).
+ *   Every argument may be NULL.
+ * tslam_tsdf_render_read: one view copied out (synchronises); NULL pointers are skipped, a
+ *   pointer for an output not asked for is TSLAM_EINVAL. */
+#define TSLAM_RENDER_DEPTH_M 1
+#define TSLAM_RENDER_DEPTH_MM 2
+#define TSLAM_RENDER_NORMAL 4
+#define TSLAM_RENDER_COLOR 8
+typedef struct {
+    int32_t width, height;
+    double fx, fy, cx, cy;
+    double min_weight;     /* a sample needs all eight corner weights >= min_weight */
+    double min_depth, max_depth;   /* metres along the camera's z axis */
+    double step_scale;     /* the fraction of the sampled distance a step advances by, (0, 1] */
+    int32_t outputs;       /* TSLAM_RENDER_* bits */
+    int32_t reserved;      /* 0 */
+} tslam_tsdf_render_params;
+int tslam_tsdf_render_init(tslam_handle* h, const tslam_tsdf_render_params* params, int max_views);
+int tslam_tsdf_render(tslam_handle* h, int pair, const double* world_T_cam, int n_views, int64_t first_frame, void* stream);
+int tslam_tsdf_render_buffers(tslam_handle* h, void** depth_m, void** depth_mm, void** normal, void** color,
+                              int64_t* view_bytes);
+int tslam_tsdf_render_read(tslam_handle* h, int view, float* depth_m, uint16_t* depth_mm, float* normal, uint8_t* color);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,6 +80,13 @@ int dense_reset(tslam_handle* h) {
             HIPCHK(hipMemset(h->tsdf.col_w, 0, sizeof(float) * nv));
         }
     }
+    if (h->rnd_on) {   // the render state stays, its images do not
+        const size_t n = (size_t)h->rnd_prm.width * h->rnd_prm.height * h->rnd_views;
+        if (h->d_rnd_depth_m) HIPCHK(hipMemset(h->d_rnd_depth_m, 0, sizeof(float) * n));
+        if (h->d_rnd_depth_mm) HIPCHK(hipMemset(h->d_rnd_depth_mm, 0, sizeof(uint16_t) * n));
+        if (h->d_rnd_normal) HIPCHK(hipMemset(h->d_rnd_normal, 0, sizeof(float) * 3 * n));
+        if (h->d_rnd_color) HIPCHK(hipMemset(h->d_rnd_color, 0, 3 * n));
+    }
     return TSLAM_OK;
 }
 
@@ -314,6 +321,159 @@ int tslam_tsdf_integrate_rig(tslam_handle* h, const tslam_tsdf_rig_camera* cams,
         HIPCHK(hipGetLastError());
         if (world_T_base) HIPCHK(hipStreamSynchronize(s));   // the staged host poses are reused
     }
+    return TSLAM_OK;
+}
+
+// -- the volume seen from a pose (k_tsdf_render.hip; thor_slam_amd/dense_render.py) ----------------
+static const int RENDER_MAX_IMAGE = 16384;
+
+int tslam_tsdf_render_init(tslam_handle* h, const tslam_tsdf_render_params* params, int max_views) {
+    if (!h || !params) return fail(TSLAM_EINVAL, "bad argument");
+    BA_FLUSH(h);
+    if (!h->tsdf_on) return fail(TSLAM_ESTATE, "no TSDF volume (tslam_tsdf_init)");
+    if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_tsdf_render_init inside a batch");
+    const tslam_tsdf_render_params p = *params;
+    if (h->tsdf.nx < 2 || h->tsdf.ny < 2 || h->tsdf.nz < 2) return fail(TSLAM_EINVAL, "rendering needs volume dims >= 2");
+    if (p.width < 1 || p.height < 1 || p.width > RENDER_MAX_IMAGE || p.height > RENDER_MAX_IMAGE)
+        return fail(TSLAM_EINVAL, "width and height must be 1..16384");
+    for (const double v : {p.fx, p.fy, p.cx, p.cy, p.min_weight, p.min_depth, p.max_depth, p.step_scale})
+        if (!std::isfinite(v)) return fail(TSLAM_EINVAL, "camera and render parameters must be finite");
+    if (!(p.fx > 0.0 && p.fy > 0.0)) return fail(TSLAM_EINVAL, "fx and fy must be > 0");
+    if (!(p.min_weight >= 0.0)) return fail(TSLAM_EINVAL, "min_weight must be >= 0");
+    if (!(p.min_depth >= 0.0 && p.max_depth > p.min_depth)) return fail(TSLAM_EINVAL, "need 0 <= min_depth < max_depth");
+    if (!(p.step_scale > 0.0 && p.step_scale <= 1.0)) return fail(TSLAM_EINVAL, "step_scale must be in (0, 1]");
+    if (p.outputs < 1 || p.outputs > 15 || p.reserved != 0) return fail(TSLAM_EINVAL, "outputs must be a bit mask 1..15 and reserved 0");
+    if (max_views < 1 || max_views > TSDF_MAX_FRAMES) return fail(TSLAM_EINVAL, "max_views must be 1..256");
+    if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
+    h->rnd_on = false;
+    // rule 1's L, on the host: the device takes no square root on the marching path
+    const size_t px = (size_t)p.width * p.height;
+    std::vector<double> L(px);
+    for (int y = 0; y < p.height; ++y) {
+        const double dc1 = ((double)y - p.cy) / p.fy;
+        for (int x = 0; x < p.width; ++x) {
+            const double dc0 = ((double)x - p.cx) / p.fx;
+            L[(size_t)y * p.width + x] = std::sqrt((dc0 * dc0 + dc1 * dc1) + 1.0);
+        }
+    }
+    int rc = dev_grow(h, (void**)&h->d_rnd_L, sizeof(double) * px);
+    if (rc == TSLAM_OK && !h->d_rnd_poses) rc = dev_alloc(h, (void**)&h->d_rnd_poses, sizeof(double) * TSDF_MAX_FRAMES * TSDF_POSE);
+    if (rc == TSLAM_OK && !h->d_rnd_wTc) rc = dev_alloc(h, (void**)&h->d_rnd_wTc, sizeof(double) * TSDF_MAX_FRAMES * 16);
+    // an output that is not asked for keeps no buffer
+    const size_t n = px * max_views;
+    auto out = [&](void** buf, int bit, size_t bytes) {
+        if (rc != TSLAM_OK) return;
+        if (p.outputs & bit) {
+            rc = dev_grow(h, buf, bytes);
+        } else if (*buf) {
+            (void)hipFree(*buf);
+            h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), *buf), h->allocs.end());
+            *buf = nullptr;
+        }
+    };
+    out((void**)&h->d_rnd_depth_m, TSLAM_RENDER_DEPTH_M, sizeof(float) * n);
+    out((void**)&h->d_rnd_depth_mm, TSLAM_RENDER_DEPTH_MM, sizeof(uint16_t) * n);
+    out((void**)&h->d_rnd_normal, TSLAM_RENDER_NORMAL, sizeof(float) * 3 * n);
+    out((void**)&h->d_rnd_color, TSLAM_RENDER_COLOR, 3 * n);
+    if (rc != TSLAM_OK) return rc;
+    HIPCHK(hipMemcpy(h->d_rnd_L, L.data(), sizeof(double) * px, hipMemcpyHostToDevice));
+    h->rnd_prm = p;
+    h->rnd_views = max_views;
+    h->rnd_on = true;
+    return TSLAM_OK;
+}
+
+int tslam_tsdf_render(tslam_handle* h, int pair, const double* world_T_cam, int n_views, int64_t first_frame, void* stream) {
+    if (!h || pair < 0 || pair >= h->P) return fail(TSLAM_EINVAL, "bad handle or pair");
+    BA_FLUSH(h);
+    if (!h->tsdf_on) return fail(TSLAM_ESTATE, "no TSDF volume (tslam_tsdf_init)");
+    if (!h->rnd_on) return fail(TSLAM_ESTATE, "no render state (tslam_tsdf_render_init)");
+    if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_tsdf_render inside a batch");
+    if (h->tsdf.nx < 2 || h->tsdf.ny < 2 || h->tsdf.nz < 2) return fail(TSLAM_EINVAL, "rendering needs volume dims >= 2");
+    if (n_views < 0 || n_views > h->rnd_views) return fail(TSLAM_EINVAL, "n_views must be 0..max_views");
+    int f0 = 0;
+    if (!world_T_cam) {   // device poses: frames of the last batch
+        f0 = (int)(first_frame - h->cur_g0);
+        if (first_frame < h->cur_g0 || f0 + n_views > h->cur_n)
+            return fail(TSLAM_EINVAL, "device poses: frames must belong to the last batch");
+    }
+    if (n_views == 0) return TSLAM_OK;
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = stream ? (hipStream_t)stream : h->last_stream;
+    const TsdfArgs& t = h->tsdf;
+    const tslam_tsdf_render_params& p = h->rnd_prm;
+    TsdfRenderArgs a{};
+    a.tsdf = t.tsdf;
+    a.weight = t.weight;
+    a.col = h->tsdf_color ? t.col : nullptr;
+    a.col_w = h->tsdf_color ? t.col_w : nullptr;
+    a.nx = t.nx;
+    a.ny = t.ny;
+    a.nz = t.nz;
+    a.ox = t.ox;
+    a.oy = t.oy;
+    a.oz = t.oz;
+    a.s = t.s;
+    a.win = h->d_tsdf_win;
+    a.W = p.width;
+    a.H = p.height;
+    a.fx = p.fx;
+    a.fy = p.fy;
+    a.cx = p.cx;
+    a.cy = p.cy;
+    a.min_weight = p.min_weight;
+    a.min_depth = p.min_depth;
+    a.max_depth = p.max_depth;
+    a.step_scale = p.step_scale;
+    a.L = h->d_rnd_L;
+    a.depth_m = h->d_rnd_depth_m;
+    a.depth_mm = h->d_rnd_depth_mm;
+    a.normal = h->d_rnd_normal;
+    a.color = h->d_rnd_color;
+    const double* wtc = nullptr;
+    if (world_T_cam) {   // staged on the stream: the next call's copy is ordered behind this call's pose kernel.
+                         // From pageable memory the runtime reads the source before it returns (and may wait for
+                         // the stream to get there); no explicit synchronise is added, and device poses never wait
+        HIPCHK(hipMemcpyAsync(h->d_rnd_wTc, world_T_cam, sizeof(double) * 16 * n_views, hipMemcpyHostToDevice, s));
+        wtc = h->d_rnd_wTc;
+    }
+    launch_tsdf_render(make_ctx(h), pair, f0, wtc, a, n_views, h->d_rnd_poses, s);
+    HIPCHK(hipGetLastError());
+    return TSLAM_OK;
+}
+
+int tslam_tsdf_render_buffers(tslam_handle* h, void** depth_m, void** depth_mm, void** normal, void** color,
+                              int64_t* view_bytes) {
+    if (!h) return fail(TSLAM_EINVAL, "null handle");
+    if (!h->rnd_on) return fail(TSLAM_ESTATE, "no render state (tslam_tsdf_render_init)");
+    if (depth_m) *depth_m = h->d_rnd_depth_m;
+    if (depth_mm) *depth_mm = h->d_rnd_depth_mm;
+    if (normal) *normal = h->d_rnd_normal;
+    if (color) *color = h->d_rnd_color;
+    if (view_bytes) {
+        const int64_t px = (int64_t)h->rnd_prm.width * h->rnd_prm.height;
+        view_bytes[0] = 4 * px;
+        view_bytes[1] = 2 * px;
+        view_bytes[2] = 12 * px;
+        view_bytes[3] = 3 * px;
+    }
+    return TSLAM_OK;
+}
+
+int tslam_tsdf_render_read(tslam_handle* h, int view, float* depth_m, uint16_t* depth_mm, float* normal, uint8_t* color) {
+    if (!h) return fail(TSLAM_EINVAL, "null handle");
+    if (!h->rnd_on) return fail(TSLAM_ESTATE, "no render state (tslam_tsdf_render_init)");
+    if (view < 0 || view >= h->rnd_views) return fail(TSLAM_EINVAL, "view out of range");
+    if ((depth_m && !h->d_rnd_depth_m) || (depth_mm && !h->d_rnd_depth_mm) || (normal && !h->d_rnd_normal) ||
+        (color && !h->d_rnd_color))
+        return fail(TSLAM_EINVAL, "an output that tslam_tsdf_render_init was not asked for");
+    BA_FLUSH(h);
+    if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
+    const size_t px = (size_t)h->rnd_prm.width * h->rnd_prm.height;
+    if (depth_m) HIPCHK(hipMemcpy(depth_m, h->d_rnd_depth_m + px * view, 4 * px, hipMemcpyDeviceToHost));
+    if (depth_mm) HIPCHK(hipMemcpy(depth_mm, h->d_rnd_depth_mm + px * view, 2 * px, hipMemcpyDeviceToHost));
+    if (normal) HIPCHK(hipMemcpy(normal, h->d_rnd_normal + 3 * px * view, 12 * px, hipMemcpyDeviceToHost));
+    if (color) HIPCHK(hipMemcpy(color, h->d_rnd_color + 3 * px * view, 3 * px, hipMemcpyDeviceToHost));
     return TSLAM_OK;
 }
 

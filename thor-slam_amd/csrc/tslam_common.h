@@ -281,7 +281,7 @@ void launch_pose_graph_cost(const double* T, const int32_t* edges, const double*
                             double* terms, double* cost, hipStream_t s);
 // TSDF volume + one integration launch (k_tsdf.hip)
 #define TSDF_MAX_FRAMES 256
-#define TSDF_POSE 13   // cam_T_world R (9), t (3), use flag
+#define TSDF_POSE 13   // R (9), t (3), use flag: cam_T_world for integration, world_T_cam (t = the centre) for rendering
 struct TsdfArgs {
     float* tsdf;
     float* weight;
@@ -357,6 +357,29 @@ struct TsdfRigArgs : TsdfArgs {
 // (device poses); host_wTb_dev: staged world_T_base [n_frames][16] or null
 void launch_tsdf_rig(const BatchCtx& c, uint64_t pairs, int f0, const double* host_wTb_dev, const TsdfRigArgs& a,
                      double* poses, hipStream_t s, const TsdfFollowCall* follow = nullptr);
+// The volume seen from a pose (k_tsdf_render.hip; thor_slam_amd/dense_render.py): n_views images of
+// one pinhole camera.  Outputs [views][H][W] (normal and color x 3); a null output is not written.
+struct TsdfRenderArgs {
+    const float* tsdf;
+    const float* weight;
+    const float* col;          // the colour layer [nv][3] (R, G, B) and its weight, or null
+    const float* col_w;
+    int nx, ny, nz;
+    double ox, oy, oz, s;
+    const TsdfWindow* win;     // as TsdfArgs::win
+    int W, H;
+    double fx, fy, cx, cy;
+    double min_weight, min_depth, max_depth, step_scale;
+    const double* L;           // [H][W] metres per unit of depth along the pixel's ray (host table)
+    const double* poses;       // [views][TSDF_POSE]: world_T_cam R rows (9), centre (3), use flag
+    float* depth_m;
+    uint16_t* depth_mm;
+    float* normal;
+    uint8_t* color;
+};
+// pair, f0, host_wTc_dev as launch_tsdf; poses: the call's table, written by its pose kernel
+void launch_tsdf_render(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev, const TsdfRenderArgs& a, int n_views,
+                        double* poses, hipStream_t s);
 // dense stereo depth (k_stereo_depth.hip): n frames of one rectified pair -> disp32 (1/32 px) and
 // depth (mm), u16 [n][H][W]; win_left / win_right: u8 [n][H][W] winner maps between its two kernels
 struct StereoDepthArgs {

@@ -251,6 +251,19 @@ struct tslam_handle {
     TsdfWindow* d_tsdf_win = nullptr; // {shift, delta}, written on the device
     float* d_tsdf_scratch = nullptr;  // the move's copy of every layer (each layer's base a multiple of 4 floats)
     size_t tsdf_scratch_cap = 0;
+    // the volume seen from a pose (tslam_tsdf_render_*): parameters, the camera's ray-length table,
+    // the call's pose table and staged host poses, and the images [rnd_views][H][W] of every
+    // output the init asked for (the others stay null)
+    bool rnd_on = false;
+    tslam_tsdf_render_params rnd_prm{};
+    int rnd_views = 0;
+    double* d_rnd_L = nullptr;        // [H][W]
+    double* d_rnd_poses = nullptr;    // [TSDF_MAX_FRAMES][TSDF_POSE]
+    double* d_rnd_wTc = nullptr;      // [TSDF_MAX_FRAMES][16]
+    float* d_rnd_depth_m = nullptr;
+    uint16_t* d_rnd_depth_mm = nullptr;
+    float* d_rnd_normal = nullptr;
+    uint8_t* d_rnd_color = nullptr;
     // dense stereo depth (tslam_stereo_depth_*): parameters, output slots and winner-map scratch
     bool sd_on = false;
     tslam_stereo_depth_params sd_prm{};

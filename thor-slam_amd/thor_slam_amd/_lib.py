@@ -123,6 +123,17 @@ class TsdfFollowParams(ctypes.Structure):
     _fields_ = [("anchor", ctypes.c_int32 * 3), ("margin", ctypes.c_int32), ("step", ctypes.c_int32)]
 
 
+class TsdfRenderParams(ctypes.Structure):
+    """tslam_tsdf_render_params: the camera and the marching rule of ``Handle.tsdf_render``
+    (thor_slam_amd/dense_render.py)."""
+    _fields_ = [
+        ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("fx", ctypes.c_double), ("fy", ctypes.c_double),
+        ("cx", ctypes.c_double), ("cy", ctypes.c_double), ("min_weight", ctypes.c_double), ("min_depth", ctypes.c_double),
+        ("max_depth", ctypes.c_double), ("step_scale", ctypes.c_double), ("outputs", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 def camera_desc(cam) -> CameraDesc:
     """A ``CameraConfig`` (intrinsics + world extrinsics) as a ``tslam_camera_desc``."""
     d = CameraDesc()
@@ -304,6 +315,14 @@ _SIGNATURES = {
     "tslam_tsdf_follow": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "tslam_tsdf_shift": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "tslam_tsdf_window": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "tslam_tsdf_render_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    "tslam_tsdf_render": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+                                         ctypes.c_void_p]),
+    "tslam_tsdf_render_buffers": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
+                                                 ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                                 ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
+    "tslam_tsdf_render_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 
@@ -968,6 +987,53 @@ class Handle:
         o = np.zeros(3, dtype=np.float64)
         _check(self.lib.tslam_tsdf_window(self.h, sh.ctypes.data, o.ctypes.data))
         return sh, o
+
+    # -- the volume seen from a pose (thor_slam_amd/dense_render.py) -----------------------------
+    def tsdf_render_init(self, width: int, height: int, fx: float, fy: float, cx: float, cy: float,
+                         min_weight: float = 1e-4, min_depth: float = 0.0, max_depth: float = 10.0,
+                         step_scale: float = 0.5, max_views: int = 1, outputs: int = 15) -> None:
+        """The camera, the marching parameters, the outputs (bit mask: 1 depth_m, 2 depth_mm,
+        4 normal, 8 color) and the most views of one ``tsdf_render`` call; after ``tsdf_init``."""
+        prm = TsdfRenderParams(int(width), int(height), float(fx), float(fy), float(cx), float(cy), float(min_weight),
+                               float(min_depth), float(max_depth), float(step_scale), int(outputs), 0)
+        _check(self.lib.tslam_tsdf_render_init(self.h, ctypes.addressof(prm), int(max_views)))
+        self._render = (int(height), int(width), int(outputs))
+
+    def tsdf_render(self, world_T_cam: np.ndarray | None = None, n_views: int | None = None, first_frame: int = 0,
+                    pair: int = 0, stream: int = 0) -> None:
+        """Views 0.. of the volume on the stream (asynchronous): at the host poses ``world_T_cam``
+        [n][4][4] (volume frame; a NaN pose gives a zero image), or with None at ``pair``'s tracked
+        device poses of frames first_frame.. of the last batch (``n_views`` of them)."""
+        poses = None
+        if world_T_cam is not None:
+            poses = np.ascontiguousarray(np.asarray(world_T_cam, dtype=np.float64).reshape(-1, 4, 4))
+            n_views = poses.shape[0] if n_views is None else n_views
+        elif n_views is None:
+            raise ValueError("n_views is needed with device poses")
+        self._render_poses = poses   # stays alive behind the asynchronous call
+        _check(self.lib.tslam_tsdf_render(self.h, int(pair), None if poses is None else poses.ctypes.data, int(n_views),
+                                          int(first_frame), ctypes.c_void_p(stream)))
+
+    def tsdf_render_buffers(self) -> tuple[dict, dict]:
+        """(device pointers, bytes of one view) per output name; 0 for an output not asked for."""
+        names = ("depth_m", "depth_mm", "normal", "color")
+        ptrs = [ctypes.c_void_p() for _ in names]
+        nbytes = (ctypes.c_int64 * 4)()
+        _check(self.lib.tslam_tsdf_render_buffers(self.h, *[ctypes.byref(p) for p in ptrs], ctypes.addressof(nbytes)))
+        return {k: int(p.value or 0) for k, p in zip(names, ptrs)}, {k: int(b) for k, b in zip(names, nbytes)}
+
+    def tsdf_render_read(self, view: int = 0) -> dict:
+        """The outputs asked for of one view (synchronises): ``depth_m`` f32 [H][W], ``depth_mm`` u16
+        [H][W], ``normal`` f32 [H][W][3], ``color`` u8 [H][W][3] (B, G, R)."""
+        if getattr(self, "_render", None) is None:   # no tsdf_render_init yet: the library says so
+            _check(self.lib.tslam_tsdf_render_read(self.h, int(view), None, None, None, None))
+        H, W, outputs = self._render
+        spec = (("depth_m", 1, (H, W), np.float32), ("depth_mm", 2, (H, W), np.uint16),
+                ("normal", 4, (H, W, 3), np.float32), ("color", 8, (H, W, 3), np.uint8))
+        out = {k: np.zeros(shape, dtype=dt) for k, bit, shape, dt in spec if outputs & bit}
+        _check(self.lib.tslam_tsdf_render_read(self.h, int(view), *[out[k].ctypes.data if k in out else None
+                                                                    for k, _, _, _ in spec]))
+        return out
 
     # -- dense stereo depth (thor_slam_amd/stereo_depth.py) ------------------------------------
     def stereo_depth_init(self, max_frames: int = 1, n_disp: int = 0, uniqueness: int = 10, lr_tol: int = 1) -> None:

@@ -160,6 +160,12 @@ class HipSlamConfig(SlamConfig):
     esdf_integrator_max_site_distance_vox: float = 1.0
     esdf_slice_min_height: float = -0.5
     esdf_slice_max_height: float = 0.5
+    # the dense map seen from a pose (get_dense_view; thor_slam_amd/dense_render.py): a ray steps by
+    # dense_view_step_scale (in (0, 1]) times the distance the volume reports, at least one voxel,
+    # out to dense_view_max_distance_m (None = tsdf_integrator_max_integration_distance_m); a sample
+    # is observed from mesh_integrator_min_weight on, as the mesh's cubes are
+    dense_view_step_scale: float = 0.5
+    dense_view_max_distance_m: float | None = None
     # dense stereo depth (thor_slam_amd/stereo_depth.py): on a stereo rig, pair 0's depth image is
     # computed on the device from the rectified images (candidate disparities 0 .. max_disparity - 1)
     # and feeds dense_map as an RGB-D camera's depth does (no colour layer: the images are gray, so
@@ -227,6 +233,11 @@ class HipSlamConfig(SlamConfig):
                 raise ValueError("voxel_size, integration distance, truncation must be > 0, max weight >= 1")
             if len(self.tsdf_dims) != 3 or min(self.tsdf_dims) < 1 or len(self.tsdf_origin) != 3:
                 raise ValueError("tsdf_dims must be 3 positive voxel counts, tsdf_origin 3 coordinates")
+        if not (isinstance(self.dense_view_step_scale, (int, float)) and 0 < self.dense_view_step_scale <= 1):
+            raise ValueError("dense_view_step_scale must be in (0, 1]")
+        if self.dense_view_max_distance_m is not None and not (
+                isinstance(self.dense_view_max_distance_m, (int, float)) and 0 < self.dense_view_max_distance_m < float("inf")):
+            raise ValueError("dense_view_max_distance_m must be None or a finite distance > 0")
         if isinstance(self.dense_cameras, str):
             if self.dense_cameras != "all":
                 raise DenseCamerasError("dense_cameras must be (), 'all' or a tuple of pair indices / source names")

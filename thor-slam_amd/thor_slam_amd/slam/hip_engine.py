@@ -68,6 +68,7 @@ from .._lib import POSE_INIT, POSE_LOST, POSE_OK, Handle, HandleGroup, SingularS
 from ..calib import (StereoRectification, confidence_from_covariance, extract_cameras, rgbd_pairs, rgbd_undistort,
                      stereo_pairs, stereo_rectify)
 from ..camera.rig import RigCalibration
+from ..dense_render import check_render_params, scaled_intrinsics, view_in_volume
 from ..dense_rig import DenseCamerasError, resolve_dense_cameras
 from ..loop import span_edges
 from ..camera.types import SynchronizedFrameSet
@@ -540,6 +541,7 @@ class HipSlamEngine(SlamEngine):
                         self._handle.stereo_depth_filter(median=cfg.stereo_depth_median, speckle_size=cfg.stereo_depth_speckle_size,
                                                          speckle_range=cfg.stereo_depth_speckle_range)
             self._sd_last = {}
+            self._view_key = None   # get_dense_view's camera (size, intrinsics, range) on the handle
             self._loop = None
             if cfg.enable_loop_closure and cfg.devices and cfg.rgbd:
                 # rank 0's ring holds only its own cameras' features (no state gather): no rig-wide
@@ -1036,6 +1038,63 @@ class HipSlamEngine(SlamEngine):
                 "voxel_size": float(cfg.voxel_size),
                 "truncation_m": cfg.tsdf_integrator_truncation_distance_vox * cfg.voxel_size,
                 "world_T_volume": self._map_offset @ self._base_T_rect}
+
+    def get_dense_view(self, world_T_view: np.ndarray | None = None, size: tuple | None = None,
+                       intrinsics: tuple | None = None) -> dict | None:
+        """The dense map seen from a camera pose (ray casting on the device, k_tsdf_render.hip; the
+        rule is thor_slam_amd/dense_render.py): ``depth`` f32 [H][W] (metres along the camera's z
+        axis), ``depth_mm`` u16 [H][W] (what ``tsdf_integrate`` reads), ``normals`` f32 [H][W][3]
+        (in the volume's frame, pointing into free space), with the colour layer ``colors`` u8
+        [H][W][3] (B, G, R); all zero where the map holds no surface.  Also ``intrinsics`` (fx, fy,
+        cx, cy), ``world_T_view``, and the volume's ``origin``, ``window_shift`` and
+        ``world_T_volume`` as ``get_dense_map`` gives them.
+
+        ``world_T_view``: the camera (optical frame, RDF) in the published world; None = pair 0's
+        rectified left camera at the newest published pose (None is returned while there is none).
+        ``size`` = (W, H) and ``intrinsics`` = (fx, fy, cx, cy): default pair 0's rectified left
+        camera, whose depth fills the map; a ``size`` alone keeps that camera's field of view.
+        None unless ``dense_map`` is on.  Synchronises."""
+        cfg = self._config
+        if not cfg.dense_map or (self._handle is None and self._shard is None):
+            return None
+        if self._shard is not None:
+            raise RuntimeError("get_dense_view does not run on a sharded rig (devices)")
+        self.flush()
+        r = self._rects[0]
+        size = (int(r.width), int(r.height)) if size is None else (int(size[0]), int(size[1]))
+        if intrinsics is None:
+            intrinsics = scaled_intrinsics((r.width, r.height), (r.fx, r.fy, r.cx, r.cy), size)
+        intrinsics = tuple(float(v) for v in intrinsics)
+        world_T_volume = self._map_offset @ self._base_T_rect
+        if world_T_view is None:
+            with self._pose_lock:
+                pose = self._latest_pose
+            if pose is None:
+                return None
+            body = np.eye(4)
+            body[:3, :3] = Rotation.from_quat(pose.rotation).as_matrix()
+            body[:3, 3] = pose.position
+            world_T_view = body @ self._base_T_rect
+        world_T_view = np.array(world_T_view, dtype=np.float64).reshape(4, 4)
+        max_depth = cfg.dense_view_max_distance_m
+        if max_depth is None:
+            max_depth = cfg.tsdf_integrator_max_integration_distance_m
+        key = (size, intrinsics, float(max_depth))
+        if self._view_key != key:   # a new camera: its ray-length table and images
+            check_render_params(size[0], size[1], *intrinsics, cfg.mesh_integrator_min_weight, 0.0, float(max_depth),
+                                cfg.dense_view_step_scale)
+            self._handle.tsdf_render_init(size[0], size[1], *intrinsics, min_weight=cfg.mesh_integrator_min_weight,
+                                          min_depth=0.0, max_depth=float(max_depth), step_scale=cfg.dense_view_step_scale,
+                                          max_views=1, outputs=15 if self._dense_color else 7)
+            self._view_key = key
+        self._handle.tsdf_render(view_in_volume(world_T_volume, world_T_view)[None])
+        out = self._handle.tsdf_render_read(0)
+        shift, origin = self._handle.tsdf_window()
+        res = {"depth": out["depth_m"], "depth_mm": out["depth_mm"], "normals": out["normal"], "intrinsics": intrinsics,
+               "world_T_view": world_T_view, "origin": origin, "window_shift": shift, "world_T_volume": world_T_volume}
+        if self._dense_color:
+            res["colors"] = out["color"]
+        return res
 
     def get_mesh(self) -> dict | None:
         """The surface mesh of the TSDF volume (marching cubes on the device, k_dense.hip):
