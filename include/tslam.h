@@ -136,7 +136,7 @@ enum tslam_buffer {
     TSLAM_BUF_STATS = 11,    /* i32 [batch][pairs][8]            status n_corr n_inl best ... */
     TSLAM_BUF_QBEST = 12,    /* u32 [batch][pairs][2][K]         (dist<<16 | idx) stereo, temporal */
     TSLAM_BUF_QSECOND = 13,  /* u32 [batch][pairs][2][K]                                      */
-    TSLAM_BUF_TBEST = 14,    /* u32 [batch][pairs][2][K]         train-side atomicMin         */
+    TSLAM_BUF_TBEST = 14,    /* u32 [batch][pairs][2][K]         train-side atomicMin, by the train's y-sorted position */
     TSLAM_BUF_YSORTED = 15,  /* u32 [ring][cams][K][4]           per level, by (y, rank): {x | y<<16, lvl | score<<16, kp index, valid} */
     TSLAM_BUF_ROWSTART = 16, /* u16 [ring][cams][sum(H_l+1)]     per level: first y-sorted position of row y */
     TSLAM_BUF_DESC_YS = 17,  /* u32 [ring][cams][K][8]           descriptors in the y-sorted order */
@@ -144,7 +144,11 @@ enum tslam_buffer {
     TSLAM_BUF_DET_FAIL = 19, /* u32 [batch][cams][levels]        1 = the last batch's image-level took the fallback */
     TSLAM_BUF_HYP = 20,      /* f64 [batch][pairs][n_hyp][4][20] P3P candidates of each RANSAC hypothesis, by
                                 ascending root: R[9] t[3] (f64; R[0] NaN = no solution), then f32 copies */
-    TSLAM_BUF_COUNT = 21
+    TSLAM_BUF_YPOS = 21,     /* u16 [ring][cams][K]              keypoint index -> position in the y-sorted order (the
+                                                                  inverse of TSLAM_BUF_YSORTED's index word; added within ABI 21) */
+    TSLAM_BUF_QTPOS = 22,    /* u16 [batch][pairs][2][K]         by query position: y-sorted position of its best train
+                                                                  (where its TSLAM_BUF_TBEST word lies; added within ABI 21) */
+    TSLAM_BUF_COUNT = 23
 };
 
 enum tslam_stage {
@@ -618,6 +622,20 @@ int tslam_ba_defer(tslam_handle* h, int defer);
  * 0 (default): each block shape's built-in capacity; N > 0: at most N candidates are kept resident
  * (a level with more takes the global sweeps). */
 int tslam_select_mode(tslam_handle* h, int mode, int resident_cap);
+/* Test hook for the matcher's train-side minima (results are identical on every path).  mode 0
+ * (default) and 2: the waves of a block merge their per-train minima in LDS, by the train's
+ * y-sorted position inside the block's window, and the block sends one atomic per touched position;
+ * 1: every wave sends its own atomics (the direct path).  merge_cap 0 (default): the built-in
+ * capacity; N > 0: at most N positions of a window are merged, the rest take the direct path in the
+ * same launch. */
+int tslam_match_mode(tslam_handle* h, int mode, int merge_cap);
+/* Path counters of the matcher (synchronises).  The first call switches counting on and returns
+ * zeros; every call returns the counts since the previous one and clears them.  counters16: per
+ * mode (stereo 0..7, temporal 8..15) [0] train minima merged in LDS, [1] sent directly, [2] global
+ * atomics of merged positions, [3] blocks that had nothing to match and wrote "no match" for their
+ * positions, [4] blocks that matched; the rest 0.  blocks_per_cu (or null): the k_match blocks the runtime places on a
+ * compute unit (4 with the merge array inside the kernel's LDS budget). */
+int tslam_match_counters(tslam_handle* h, uint32_t* counters16, int* blocks_per_cu);
 /* Measurement: `reps` back-to-back k_ba_schur launches on pair `pair`'s last solved window (the
  * kernel only rewrites its own outputs), between two HIP events on `stream`: the average launch
  * duration and the algorithmic flops per launch (for the FP64 MFMA roofline, without per-launch

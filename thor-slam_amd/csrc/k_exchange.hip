@@ -68,6 +68,16 @@ __global__ __launch_bounds__(256) void k_stream_blocks(BatchCtx c, int64_t first
         if (PACK) copy_piece(b + off[p], ring[p], len[p]);
         else copy_piece(ring[p], b + off[p], len[p]);
     }
+    // unpack: the keypoint index -> position lookup is not part of the block; it is the inverse of
+    // the records' index word (ys[p].z), rebuilt from the block's records as select wrote it
+    if (!PACK) {
+        const uint4* rec = reinterpret_cast<const uint4*>(b + sb.ys);
+        uint16_t* yp = c.ypos + sc * K;
+        for (int64_t i = threadIdx.x; i < K; i += blockDim.x) {
+            const uint32_t z = rec[i].z;
+            if (z < (uint32_t)K) yp[z] = (uint16_t)i;
+        }
+    }
 }
 
 // the per-item copy of k_stream_blocks (frame g, camera cam <-> block b)
@@ -89,6 +99,16 @@ __device__ __forceinline__ void stream_block_item(const BatchCtx& c, int64_t g, 
     for (int p = 0; p < 5; ++p) {
         if (PACK) copy_piece(b + off[p], ring[p], len[p]);
         else copy_piece(ring[p], b + off[p], len[p]);
+    }
+    // unpack: the keypoint index -> position lookup is not part of the block; it is the inverse of
+    // the records' index word (ys[p].z), rebuilt from the block's records as select wrote it
+    if (!PACK) {
+        const uint4* rec = reinterpret_cast<const uint4*>(b + sb.ys);
+        uint16_t* yp = c.ypos + sc * K;
+        for (int64_t i = threadIdx.x; i < K; i += blockDim.x) {
+            const uint32_t z = rec[i].z;
+            if (z < (uint32_t)K) yp[z] = (uint16_t)i;
+        }
     }
 }
 

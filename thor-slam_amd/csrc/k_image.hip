@@ -1226,12 +1226,17 @@ __device__ __forceinline__ void select_body(const BatchCtx& c, int img, int l, i
     // y-sorted order of this level (by y, then rank) + row-start table, for band-limited matching
     uint4* ys = c.ys + ((size_t)slot * c.C + cam) * c.g.K + c.g.koff[l];
     uint16_t* rs = c.rowstart + ((size_t)slot * c.C + cam) * c.g.rs_total + c.g.rs_off[l];
+    // ypos: the inverse of the records' index word (keypoint index -> y-sorted position), for k_match's tbest
+    uint16_t* yp = c.ypos + ((size_t)slot * c.C + cam) * c.g.K;
     auto record = [&](int rank) -> uint4 {
         const uint32_t k = s_keys[rank];
         return {(k & 2047u) | (((k >> 11) & 2047u) << 16), (uint32_t)l | ((255u - (k >> 22)) << 16),
                 (uint32_t)(c.g.koff[l] + rank), 1u};
     };
-    for (int i = nsel + threadIdx.x; i < Kl; i += NT) ys[i] = {0u, (uint32_t)l, (uint32_t)(c.g.koff[l] + i), 0u};
+    for (int i = nsel + threadIdx.x; i < Kl; i += NT) {
+        ys[i] = {0u, (uint32_t)l, (uint32_t)(c.g.koff[l] + i), 0u};
+        yp[c.g.koff[l] + i] = (uint16_t)(c.g.koff[l] + i);
+    }
     if (counting) {
         // rows: counts -> exclusive offsets (= rowstart), bucket ranks by row, order by rank
         // (s_a and s_fill are zero: zeroed at the top or after the radix pass that used them,
@@ -1251,6 +1256,7 @@ __device__ __forceinline__ void select_body(const BatchCtx& c, int img, int l, i
             int r = 0;
             for (int j = lo; j < lo + n; ++j) r += s_tmp[j] < i;
             ys[lo + r] = record((int)i);
+            yp[c.g.koff[l] + i] = (uint16_t)(c.g.koff[l] + lo + r);
         }
     } else {
         // bitonic on (y << 13 | rank) in the scratch half is not possible here (nsel > half):
@@ -1264,6 +1270,7 @@ __device__ __forceinline__ void select_body(const BatchCtx& c, int img, int l, i
             const int rank = (int)(yk[i] & 8191u);
             const uint2 e = *reinterpret_cast<const uint2*>(kp + 2 * rank);
             ys[i] = {e.x, e.y, (uint32_t)(c.g.koff[l] + rank), 1u};
+            yp[c.g.koff[l] + rank] = (uint16_t)(c.g.koff[l] + i);
         }
         for (int y = threadIdx.x; y <= Hl; y += NT) {
             const uint32_t target = (uint32_t)y << 13;

@@ -25,14 +25,29 @@
 // slot (0..31) as the index: a wave's queries take their slots in keypoint-index order, so slot
 // order is query order.  Slot 2 * reg + h is MFMA row (reg & 3) + 8 (reg >> 2) + 4 h, i.e. the
 // row accumulator register reg of lane half h holds, so the slot's low bit is the lane half (ORed
-// in after the register minimum).  One global atomicMin per train and wave tile publishes it
-// in the (distance << 16 | query) format the refinement kernels read.
+// in after the register minimum).  It is published in the (distance << 16 | query) format the
+// refinement kernels read: the waves of a block first combine their minima in LDS, by the train's
+// y-sorted position inside the block's window (ds_min), and after the walk the block sends one
+// global atomicMin per touched position; a position past the array's capacity (and every position
+// on the direct path, tslam_match_mode) goes to tbest from the wave that found it.  Global atomics
+// run at the memory side, one 64-byte request per lane when the addresses scatter: merging removes
+// a block's repeats of a train, and tbest is indexed by the train's y-sorted position (koff[l] +
+// position), so a block's flush covers one contiguous range.  The query's best-train key keeps the
+// keypoint index (the tie-break orders by it); the epilogue looks its position up in ypos (written
+// by select beside ys) and stores it beside qbest (qtpos), where the refinement finds tbest's word
+// (profiles/match_tbest_probe.txt).
 #include "tslam_common.h"
 
 #define TS_MQ 128          // queries per k_match block (4 waves x one 32-row MFMA tile)
 #define TS_MRED_PITCH 33   // (best, second) rows of the final per-slot reduction, padded
 #define TS_MRING 1024      // compacted trains per walk round (the ring shares the reduction's LDS)
 #define TS_MCHUNKS 6       // 64-position chunks whose record loads are in flight together
+// tslam_match_counters: per mode (stereo 0..7, temporal 8..15)
+#define TS_MCNT_MERGED 0   // train minima merged in LDS
+#define TS_MCNT_DIRECT 1   // ... sent straight to tbest (past the merge capacity, or the direct path)
+#define TS_MCNT_FLUSHED 2  // global atomics of the blocks' merged positions
+#define TS_MCNT_EMPTY 3    // blocks that had nothing to match and wrote "no match"
+#define TS_MCNT_WALKED 4   // blocks that matched
 
 typedef int v8i_t __attribute__((ext_vector_type(8)));
 typedef float v16f_t __attribute__((ext_vector_type(16)));
@@ -56,7 +71,10 @@ __device__ __forceinline__ uint32_t key_dist(uint32_t key) {   // distance of a 
     return (uint32_t)__uint_as_float(key & 0xFFFF8000u);
 }
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_match(BatchCtx c) {
+// CNT: the build that counts its paths for tslam_match_counters (k_match_counted); the shipped
+// kernel holds none of that code
+template <bool CNT>
+__device__ __forceinline__ void match_body(const BatchCtx& c) {
     TS_BACK_PRIO;
     // per wave: the compacted-train ring during the walk, then the (best, second) reduction
     __shared__ __attribute__((aligned(16))) uint2 s_red[4][32 * TS_MRED_PITCH];
@@ -72,6 +90,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     // [wave][slot & 1][slot >> 1]: lane half h reads its 16 accumulator rows as four 16-byte words
     __shared__ __attribute__((aligned(16))) uint32_t s_sg[4][2][16];
     __shared__ __attribute__((aligned(16))) float s_spc[4][2][16];
+    // The block's train-side minima (distance << 16 | query) by y-sorted train position minus the
+    // block's window base: the waves of a block reach the same trains (temporal: the x-quartile
+    // boxes overlap 2:1), so they meet here (ds_min) and each touched position leaves the CU as
+    // one global atomic after the walk.  TS_MTB fills the 40 KB that keep 4 blocks on a CU.
+    __shared__ uint32_t s_tb[TS_MTB];
     // blockIdx.y: the temporal blocks (the heavy ones: a window of rows, not a row band) of every
     // frame first, then the stereo blocks, so the short stereo blocks fill the launch's tail
     // (stereo-only launches, match_modes == 1: blockIdx.y = f * P + p, all stereo)
@@ -82,11 +105,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     const int p = c.pair0 + fl % c.npair;
     const int f = fl / c.npair;
     const int64_t g = c.g0 + f;
-    if (mode == 1 && g == 0) return;          // no previous frame
-    if (mode == 0 && c.rgbd) return;          // RGB-D: depth replaces stereo matching
     int l = 0;
     while (l + 1 < c.g.n_levels && (int)blockIdx.x >= c.g.qtile_start[l + 1]) ++l;
     const int tile = blockIdx.x - c.g.qtile_start[l];
+    const int q0 = tile * TS_MQ;
+    const size_t mbase = (((size_t)f * c.P + p) * 2 + mode) * c.g.K;
+    // A block with nothing to match writes "no match" for its tile's positions of the level itself
+    // (qbest is not cleared before the launch).  Every such return is block-uniform.
+    auto no_match = [&]() {
+        if ((int)threadIdx.x < TS_MQ && q0 + (int)threadIdx.x < c.g.Kq[l]) c.qbest[mbase + c.g.koff[l] + q0 + threadIdx.x] = 0xFFFFFFFFu;
+        if (CNT && threadIdx.x == 0) atomicAdd(&c.match_cnt[8 * mode + TS_MCNT_EMPTY], 1u);
+    };
+    if ((mode == 1 && g == 0) ||              // no previous frame
+        (mode == 0 && c.rgbd)) {              // RGB-D: depth replaces stereo matching
+        no_match();
+        return;
+    }
     const int slot = ring_slot(c, g);
     const int qcam = c.cpp * p;
     const int tslot = mode == 0 ? slot : ring_slot(c, g - 1);
@@ -94,15 +128,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     const int K = c.g.K;
     const int qn = c.kcount[((size_t)slot * c.C + qcam) * c.g.n_levels + l];
     const int tn = c.kcount[((size_t)tslot * c.C + tcam) * c.g.n_levels + l];
-    const int q0 = tile * TS_MQ;
-    if (q0 >= qn || tn == 0) return;          // block-uniform
+    if (q0 >= qn || tn == 0) {
+        no_match();
+        return;
+    }
+    if (CNT && threadIdx.x == 0) atomicAdd(&c.match_cnt[8 * mode + TS_MCNT_WALKED], 1u);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ci = lane & 31, h = lane >> 5;  // MFMA column / row index, lane half (k half)
     const size_t qbase = ((size_t)slot * c.C + qcam) * K;
     const size_t tbase = ((size_t)tslot * c.C + tcam) * K;
-    const size_t mbase = (((size_t)f * c.P + p) * 2 + mode) * K;
     const uint4* qys = c.ys + qbase + c.g.koff[l];           // y-sorted records of the level
     const uint4* tys = c.ys + tbase + c.g.koff[l];
+    uint32_t* const tb = c.tbest + mbase + c.g.koff[l];   // the level's train minima, by y-sorted position
     const uint4* qdesc = reinterpret_cast<const uint4*>(c.desc_ys + (qbase + c.g.koff[l]) * 8);
     const uint4* tdesc = reinterpret_cast<const uint4*>(c.desc_ys + (tbase + c.g.koff[l]) * 8);
     const uint16_t* trs = c.rowstart + ((size_t)tslot * c.C + tcam) * c.g.rs_total + c.g.rs_off[l];
@@ -137,6 +174,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
             wt0 = (int)trs[max(0, wy0 - reach)];
             wt1 = (int)trs[min(Hl - 1, wy1 + reach) + 1];
         }
+    }
+    // the block's train rows (the union of its waves'; temporal: every wave's own), the base and
+    // extent of the merge array; cleared here, before the barrier that ends the setup
+    const uint32_t mcap = (uint32_t)min(c.mp.merge_cap, TS_MTB);
+    int bt0 = 0, bt1 = 0;
+    if (mcap) {
+        const int by0 = (int)(s_qrec[0].x >> 16), by1 = (int)(s_qrec[nq - 1].x >> 16);
+        bt0 = __builtin_amdgcn_readfirstlane((int)trs[max(0, by0 - reach)]);
+        bt1 = __builtin_amdgcn_readfirstlane((int)trs[min(Hl - 1, by1 + reach) + 1]);
+        for (int i = threadIdx.x; i < min((int)mcap, bt1 - bt0); i += 256) s_tb[i] = 0xFFFFFFFFu;
     }
     int bi = 32 * wave + ci;
     if (mode == 1) {
@@ -330,10 +377,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            // flush: each train's (distance, query) minimum over the wave's queries
+            // flush: each train's (distance, query) minimum over the wave's queries, into the block's
+            // merge array or, past its capacity, straight into tbest (both by position)
             for (uint32_t k = (uint32_t)lane; k < n; k += 64) {
                 const uint2 e = ring[k];
-                if (e.x < 0x7F800000u) atomicMin(&c.tbest[mbase + (e.y >> 16)], key_dist(e.x & ~31u) << 16 | s_sq[wave][e.x & 31u]);
+                const bool hit = e.x < 0x7F800000u;
+                const uint32_t rel = (e.y & 0xFFFFu) - (uint32_t)bt0;
+                if (hit) {
+                    const uint32_t v = key_dist(e.x & ~31u) << 16 | s_sq[wave][e.x & 31u];
+                    if (rel < mcap)
+                        atomicMin(&s_tb[rel], v);
+                    else
+                        atomicMin(&tb[e.y & 0xFFFFu], v);
+                }
+                if (CNT) {
+                    const uint32_t nm = (uint32_t)__popcll(__ballot(hit && rel < mcap)), nd = (uint32_t)__popcll(__ballot(hit && rel >= mcap));
+                    if (lane == 0 && nm) atomicAdd(&c.match_cnt[8 * mode + TS_MCNT_MERGED], nm);
+                    if (lane == 0 && nd) atomicAdd(&c.match_cnt[8 * mode + TS_MCNT_DIRECT], nd);
+                }
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the ring is refilled by the next round
@@ -364,11 +425,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
         b = min(b, ob);
     }
     // stored by the query's y-sorted position (the refinement kernels load them beside its record)
+    // An empty slot stands for a position past the image's count: inside the level it gets the "no
+    // match" word (no memset of qbest: every position of a level is some block's to write).
     const uint32_t qk = s_sq[wave][ci];
-    if (h == 0 && qk != 0xFFFFFFFFu) {
-        const size_t qp = mbase + c.g.koff[l] + q0 + s_si[wave][ci];
-        c.qbest[qp] = b < 0x7F800000u ? key_dist(b) << 16 | (b & 0x7FFFu) : 0xFFFFFFFFu;
-        c.qsecond[qp] = s2 < 0x7F800000u ? key_dist(s2) : 256u;
+    const int qpos = q0 + (int)s_si[wave][ci];
+    if (h == 0 && qpos < c.g.Kq[l]) {
+        const size_t qp = mbase + c.g.koff[l] + qpos;
+        const bool found = qk != 0xFFFFFFFFu && b < 0x7F800000u;
+        c.qbest[qp] = found ? key_dist(b) << 16 | (b & 0x7FFFu) : 0xFFFFFFFFu;
+        if (qk != 0xFFFFFFFFu) c.qsecond[qp] = s2 < 0x7F800000u ? key_dist(s2) : 256u;
+        // where the best train's tbest word lies (the key carries its keypoint index: the tie-break
+        // orders by index); one gather per wave, so the refinement loads tbest in its second round
+        c.qtpos[qp] = found ? c.ypos[tbase + (b & 0x7FFFu)] : (uint16_t)0;
+    }
+    // the block's merged train minima: one global atomic per position that any wave touched
+    if (mcap) {
+        __syncthreads();
+        const int len = min((int)mcap, bt1 - bt0);
+        uint32_t na = 0;
+        for (int i = threadIdx.x; i < len; i += 256) {
+            const uint32_t v = s_tb[i];
+            if (v != 0xFFFFFFFFu) {
+                atomicMin(&tb[bt0 + i], v);   // a contiguous range of tbest
+                ++na;
+            }
+        }
+        if (CNT && na) atomicAdd(&c.match_cnt[8 * mode + TS_MCNT_FLUSHED], na);
     }
 }
 
@@ -518,15 +600,16 @@ __device__ __forceinline__ void temporal_store(double* out_uv, int j, int l, int
 // branch behind another load's wait.
 struct MatchRef {
     uint32_t qb, sd, tb;
-    int j;
+    int j, tp;
 };
 __device__ __forceinline__ void match_query(const BatchCtx& c, size_t mbase, int pos, MatchRef* m) {
     m->qb = c.qbest[mbase + pos];
     m->sd = c.qsecond[mbase + pos];
+    m->tp = c.qtpos[mbase + pos];   // < K always: a position, or 0 beside "no match"
     m->j = m->qb == 0xFFFFFFFFu ? 0 : (int)(m->qb & 0xFFFF);
 }
 __device__ __forceinline__ void match_train(const BatchCtx& c, size_t mbase, size_t tkb, MatchRef* m, uint32_t* tkp) {
-    m->tb = c.tbest[mbase + m->j];
+    m->tb = c.tbest[mbase + m->tp];
     *tkp = c.kps[(tkb + m->j) * 2];
 }
 __device__ __forceinline__ int match_accept(const BatchCtx& c, const MatchRef& m, int qi, bool ok) {
@@ -810,11 +893,27 @@ __global__ __launch_bounds__(256) void k_refine_pair(BatchCtx c) {
     }
 }
 
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_match(BatchCtx c) { match_body<false>(c); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_match_counted(BatchCtx c) { match_body<true>(c); }
+
+static void launch_k_match(const BatchCtx& c, dim3 grid, hipStream_t s) {
+    if (c.match_cnt)
+        hipLaunchKernelGGL(k_match_counted, grid, dim3(256), 0, s, c);
+    else
+        hipLaunchKernelGGL(k_match, grid, dim3(256), 0, s, c);
+}
+
+int match_blocks_per_cu() {
+    int n = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_match, 256, 0) == hipSuccess ? n : -1;
+}
+
+// tbest takes atomic minima, so it starts from all ones; qbest needs no clearing: k_match writes
+// every position of every level it is launched for
 void launch_match(const BatchCtx& c, hipStream_t s) {
     (void)hipMemsetAsync(c.tbest, 0xFF, sizeof(uint32_t) * (size_t)c.n * c.P * 2 * c.g.K, s);
-    (void)hipMemsetAsync(c.qbest, 0xFF, sizeof(uint32_t) * (size_t)c.n * c.P * 2 * c.g.K, s);
     dim3 grid(c.g.total_qtiles, c.n * c.npair * (c.match_modes == 1 ? 1 : 2));
-    hipLaunchKernelGGL(k_match, grid, dim3(256), 0, s, c);
+    launch_k_match(c, grid, s);
 }
 
 // Stereo matching + refinement only (the sharded rig's pre-pass for the frame before a rank's
@@ -823,8 +922,7 @@ void launch_match_stereo(const BatchCtx& c, hipStream_t s) {
     BatchCtx st = c;
     st.match_modes = 1;
     (void)hipMemsetAsync(st.tbest, 0xFF, sizeof(uint32_t) * (size_t)st.n * st.P * 2 * st.g.K, s);
-    (void)hipMemsetAsync(st.qbest, 0xFF, sizeof(uint32_t) * (size_t)st.n * st.P * 2 * st.g.K, s);
-    hipLaunchKernelGGL(k_match, dim3(st.g.total_qtiles, st.n * st.npair), dim3(256), 0, s, st);
+    launch_k_match(st, dim3(st.g.total_qtiles, st.n * st.npair), s);
     hipLaunchKernelGGL(k_refine_stereo, dim3(xcd_grid(st.n * st.npair, (st.g.K + TS_RS_QPB - 1) / TS_RS_QPB)), dim3(256), 0, s, st);
 }
 

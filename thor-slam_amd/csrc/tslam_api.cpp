@@ -180,6 +180,8 @@ BatchCtx make_ctx(tslam_handle* h) {
     c.qbest = (uint32_t*)h->buf[TSLAM_BUF_QBEST].ptr;
     c.qsecond = (uint32_t*)h->buf[TSLAM_BUF_QSECOND].ptr;
     c.tbest = (uint32_t*)h->buf[TSLAM_BUF_TBEST].ptr;
+    c.ypos = (uint16_t*)h->buf[TSLAM_BUF_YPOS].ptr;
+    c.qtpos = (uint16_t*)h->buf[TSLAM_BUF_QTPOS].ptr;
     c.stereo = (int32_t*)h->buf[TSLAM_BUF_STEREO].ptr;
     c.disp = (double*)h->buf[TSLAM_BUF_DISP].ptr;
     c.temporal = (int32_t*)h->buf[TSLAM_BUF_TEMPORAL].ptr;
@@ -210,6 +212,8 @@ BatchCtx make_ctx(tslam_handle* h) {
     c.mp.max_disp = h->prm.max_disparity;
     c.mp.window = h->prm.temporal_window;
     c.mp.refine_split = h->prm.match_refine;
+    c.mp.merge_cap = h->match_mode == 1 ? 0 : h->match_cap > 0 ? std::min(h->match_cap, TS_MTB) : TS_MTB;
+    c.match_cnt = h->d_match_cnt;
     c.pp.n_hyp = h->prm.ransac_hypotheses;
     c.pp.iters = h->prm.refine_iters;
     c.pp.min_inliers = h->prm.min_inliers;
@@ -381,6 +385,8 @@ int tslam_create(const tslam_stereo_desc* pairs, const tslam_params* params, int
         {TSLAM_BUF_ROWSTART, R, C * (int64_t)h->g.rs_total * 2},
         {TSLAM_BUF_DET_THR, 1, C * L * 4},
         {TSLAM_BUF_DET_FAIL, B, C * L * 4},
+        {TSLAM_BUF_YPOS, R, C * K * 2},
+        {TSLAM_BUF_QTPOS, B, P * 2 * K * 2},
         {TSLAM_BUF_HYP, B, P * 4 * (int64_t)p.ransac_hypotheses * TS_HYP_DOUBLES * 8},
     };
     int rc = TSLAM_OK;
@@ -865,6 +871,27 @@ int tslam_select_mode(tslam_handle* h, int mode, int resident_cap) {
     if (!h || mode < 0 || mode > 2 || resident_cap < 0) return fail(TSLAM_EINVAL, "bad handle, select mode or capacity");
     h->sel_mode = mode;
     h->sel_rcap = resident_cap;
+    return TSLAM_OK;
+}
+
+int tslam_match_mode(tslam_handle* h, int mode, int merge_cap) {
+    if (!h || mode < 0 || mode > 2 || merge_cap < 0) return fail(TSLAM_EINVAL, "bad handle, match mode or capacity");
+    h->match_mode = mode;
+    h->match_cap = merge_cap;
+    return TSLAM_OK;
+}
+
+int tslam_match_counters(tslam_handle* h, uint32_t* counters16, int* blocks_per_cu) {
+    if (!h) return fail(TSLAM_EINVAL, "bad handle");
+    int rc = tslam_sync(h);
+    if (rc != TSLAM_OK) return rc;
+    if (!h->d_match_cnt) {
+        if ((rc = dev_alloc(h, (void**)&h->d_match_cnt, sizeof(uint32_t) * 16)) != TSLAM_OK) return rc;
+    }
+    if (counters16) HIPCHK(hipMemcpy(counters16, h->d_match_cnt, sizeof(uint32_t) * 16, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemset(h->d_match_cnt, 0, sizeof(uint32_t) * 16));
+    HIPCHK(hipDeviceSynchronize());
+    if (blocks_per_cu) *blocks_per_cu = match_blocks_per_cu();
     return TSLAM_OK;
 }
 

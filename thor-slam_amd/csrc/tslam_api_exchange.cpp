@@ -14,6 +14,7 @@ static BatchCtx range_ctx(const BatchCtx& c, int lo, int hi) {
     r.qbest += f * P * 2 * K;
     r.qsecond += f * P * 2 * K;
     r.tbest += f * P * 2 * K;
+    r.qtpos += f * P * 2 * K;
     r.tuv += f * P * K * 2;
     r.corr += f * P * K * TS_CORR_DOUBLES;
     r.pose += f * P * TS_POSE_DOUBLES;

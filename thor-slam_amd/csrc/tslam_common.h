@@ -15,7 +15,9 @@
 //   ys       u32x4 [R][C][K]  desc_ys u32 [R][C][K][8]  per level, keypoints sorted by (y, rank):
 //            {xy, level | score<<16, kp index, valid} and their descriptors (contiguous match staging)
 //   rowstart u16 [R][C][sum(H_l+1)]  per level: first y-sorted position of row y
-//   qbest/qsecond/tbest u32 [B][P][2][K]   matching scratch (mode 0 stereo, 1 temporal)
+//   qbest/qsecond/tbest u32 [B][P][2][K]   matching scratch (mode 0 stereo, 1 temporal): qbest, qsecond by
+//            the query's y-sorted position, tbest by the train's; qtpos u16 [B][P][2][K] that train position
+//   ypos     u16 [R][C][K]           keypoint index -> y-sorted position (the inverse of ys' index word)
 //   stereo   i32 [R][P][K]  disp f64 [R][P][K]        stereo match + refined disparity of left kps
 //            (RGB-D: disp = fx / Z from the aligned depth, a virtual 1 m baseline; stereo = k or -1)
 //   temporal i32 [R][P][K]  tuv  f64 [B][P][K][2]     temporal match + refined (u, v) at t
@@ -33,6 +35,7 @@
 #define TS_DET_HALO 4
 #define TS_RECT_BAND 32
 #define TS_MATCH_CHUNK 512
+#define TS_MTB 896         // k_match: entries of a block's train-side merge array (k_match.hip)
 #define TS_SAD_HALF 5
 #define TS_SAD_RANGE 2
 #define TS_POSE_DOUBLES 68
@@ -84,6 +87,7 @@ struct PairCalib {
 struct MatchParams {
     int max_hamming, ratio_pct, row_tol, max_disp, window;
     int refine_split;   // stereo + temporal refinement: 0 one fused kernel (k_refine_pair), 1 the two kernels
+    int merge_cap;      // k_match: train positions per block merged in LDS before tbest (0: none; tslam_match_mode)
 };
 
 struct PoseParams {
@@ -135,7 +139,9 @@ struct BatchCtx {
     uint16_t* rowstart;    // [R][C][rs_total]
     uint32_t* qbest;
     uint32_t* qsecond;
-    uint32_t* tbest;
+    uint32_t* tbest;       // [B][P][2][K] by the train's y-sorted position
+    uint16_t* ypos;        // [R][C][K] keypoint index -> y-sorted position (select, the sharded import)
+    uint16_t* qtpos;       // [B][P][2][K] by query position: ypos of its best train
     int32_t* stereo;
     double* disp;
     int32_t* temporal;
@@ -160,6 +166,7 @@ struct BatchCtx {
     const uint32_t* det_thr;      // [C][L]
     uint32_t* det_thr_acc;        // [C][L]
     uint32_t* det_fail;           // [B][C][L]
+    uint32_t* match_cnt;          // [16] k_match path counters (tslam_match_counters) or null
 
     const uint32_t* brief_table;  // [30][256] LDS patch byte offsets of the two points (lo | hi << 16)
     const int64_t* wedges;        // [31][2]
@@ -202,6 +209,7 @@ void launch_detect(const BatchCtx& c, hipStream_t s);
 void launch_select(const BatchCtx& c, hipStream_t s, int mode, int rcap);   // tslam_select_mode
 void launch_describe(const BatchCtx& c, hipStream_t s);
 void launch_match(const BatchCtx& c, hipStream_t s);
+int match_blocks_per_cu();   // k_match blocks the runtime places on a CU (tslam_match_counters)
 void launch_match_refine(const BatchCtx& c, hipStream_t s);
 void launch_match_stereo(const BatchCtx& c, hipStream_t s);
 void launch_pose(const BatchCtx& c, hipStream_t s);

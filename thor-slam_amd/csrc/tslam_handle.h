@@ -118,6 +118,10 @@ struct tslam_handle {
     // tslam_select_mode: the path of k_select (0 auto, 1 global sweeps, 2 resident wherever it fits)
     // and a cap on the candidates kept resident (0: each block shape's own capacity)
     int sel_mode = 0, sel_rcap = 0;
+    // tslam_match_mode: k_match's train-side flush (0 auto, 1 direct, 2 merged per block), a cap on
+    // the merge array's entries (0: TS_MTB), and the path counters tslam_match_counters switches on
+    int match_mode = 0, match_cap = 0;
+    uint32_t* d_match_cnt = nullptr;
     struct {
         bool pending = false;
         BatchCtx c{};

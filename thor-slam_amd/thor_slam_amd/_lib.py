@@ -24,7 +24,7 @@ BUF = {
     "pyramid": 0, "smooth": 1, "keypoints": 2, "kcount": 3, "desc": 4, "stereo": 5, "disp": 6,
     "temporal": 7, "temporal_uv": 8, "corr": 9, "pose": 10, "stats": 11, "qbest": 12,
     "qsecond": 13, "tbest": 14, "ysorted": 15, "rowstart": 16, "desc_ys": 17, "det_thr": 18, "det_fail": 19,
-    "hyp": 20,
+    "hyp": 20, "ypos": 21, "qtpos": 22,
 }
 STAGE = {"rectify": 0, "detect": 1, "describe": 2, "match": 3, "pose": 4, "all": 5, "ba": 6}
 # single kernels, in pipeline order (bench.py times each with HIP events)
@@ -245,6 +245,8 @@ _SIGNATURES = {
     "tslam_ba_split_solve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "tslam_ba_defer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "tslam_select_mode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
+    "tslam_match_mode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
+    "tslam_match_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int)]),
     "tslam_ba_inertial": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
                                          ctypes.c_void_p, ctypes.c_double]),
     "tslam_ba_inertial_factor": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p,
@@ -381,6 +383,7 @@ def _check(rc: int) -> None:
 RANSAC_MODE = {"auto": 0, "exhaustive": 1, "bounded": 2}   # tslam_params.ransac_mode
 MATCH_REFINE = {"auto": 0, "split": 1}   # tslam_params.match_refine
 SELECT_MODE = {"auto": 0, "generic": 1, "resident": 2}   # tslam_select_mode
+MATCH_MODE = {"auto": 0, "direct": 1, "merged": 2}   # tslam_match_mode
 
 
 def make_params(cfg: HipSlamConfig, max_batch: int, n_pairs: int, ransac_splits: int = 0,
@@ -1192,6 +1195,22 @@ class Handle:
         """``tslam_select_mode`` (test hook): the top-K selection's path, ``auto`` / ``generic`` (global
         sweeps) / ``resident`` (LDS wherever it fits), and a cap on the resident candidates (0: built in)."""
         _check(self.lib.tslam_select_mode(self.h, SELECT_MODE[mode], int(resident_cap)))
+
+    def match_mode(self, mode: str = "auto", merge_cap: int = 0) -> None:
+        """``tslam_match_mode`` (test hook): k_match's train-side flush, ``auto`` / ``direct`` (every wave's
+        own atomics) / ``merged`` (per block in LDS), and a cap on the merged window positions (0: built in)."""
+        _check(self.lib.tslam_match_mode(self.h, MATCH_MODE[mode], int(merge_cap)))
+
+    def match_counters(self) -> dict:
+        """``tslam_match_counters``: the matcher's path counts since the last call (the first call switches
+        counting on), per mode ``merged`` / ``direct`` / ``flushed`` / ``empty_blocks`` / ``walked_blocks``, and ``blocks_per_cu``."""
+        cnt = (ctypes.c_uint32 * 16)()
+        bpc = ctypes.c_int(0)
+        _check(self.lib.tslam_match_counters(self.h, cnt, ctypes.byref(bpc)))
+        names = ("merged", "direct", "flushed", "empty_blocks", "walked_blocks")
+        out = {m: {k: int(cnt[8 * i + j]) for j, k in enumerate(names)} for i, m in enumerate(("stereo", "temporal"))}
+        out["blocks_per_cu"] = bpc.value
+        return out
 
     def ba_graph(self, enable: bool) -> None:
         """Pair windows' keyframe chains from captured hipGraphs (default) or direct launches (tslam.h)."""
