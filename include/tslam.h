@@ -971,6 +971,60 @@ int tslam_tsdf_render_buffers(tslam_handle* h, void** depth_m, void** depth_mm, 
                               int64_t* view_bytes);
 int tslam_tsdf_render_read(tslam_handle* h, int view, float* depth_m, uint16_t* depth_mm, float* normal, uint8_t* color);
 
+/* Dense frame-to-model alignment: projective point-to-plane ICP of depth frames against the ray-cast
+ * map (added within ABI 21: five new symbols and a struct; nothing else changes, and a handle that
+ * calls none of them behaves as before).  Spec: thor_slam_amd/dense_align.py.  For every frame the
+ * volume is rendered at the frame's initial pose T0 with `pair`'s rectified camera, and the pose is
+ * refined by `iterations` Gauss-Newton steps of the point-to-plane error between the frame's depth
+ * and that view; all of it is queued on the stream, nothing waits.  The result corrects the pose the
+ * frame is integrated with (tslam_tsdf_integrate_aligned); tracking and the poses tslam_read_poses
+ * returns are not touched.
+ *
+ * tslam_tsdf_align_init: the camera (`pair`; rect != 0: the depth lives in the pair's rectified
+ *   camera, as for tslam_tsdf_integrate_rect), the parameters and the most frames of one call
+ *   (1..256).  NULL params frees the state.  TSLAM_ESTATE without a volume or inside a batch;
+ *   TSLAM_EINVAL unless the volume has dims >= 2, 1 <= iterations <= 64, min_inliers >= 6,
+ *   max_distance, max_depth, max_translation > 0, min_weight >= 0, 0 < step_scale <= 1,
+ *   0 < max_rotation <= pi, eps_* >= 0, 0 < min_pivot < 1 (all finite) and reserved 0.
+ *   tslam_reset keeps the state; tslam_tsdf_init frees it.
+ * tslam_tsdf_align: n_frames (0..max_frames) depth images (device, u16 mm, stride_bytes apart, the
+ *   format and the lookup of tslam_tsdf_integrate) on `stream` (NULL: the handle's last stream).
+ *   world_T_cam: [n_frames][16] on the host (staged as tslam_tsdf_render stages its poses; a pose
+ *   whose first element is not finite is UNUSED), or NULL: frames first_frame.. of the last batch
+ *   with the pair's device-resident chained poses, untracked frames UNUSED.
+ * tslam_tsdf_align_read: the last call's results of frames 0 .. min(max_frames, n_frames) - 1
+ *   (synchronises); NULL pointers are skipped.  world_T_cam [n][16]: the aligned pose when the
+ *   status is TSLAM_ALIGN_OK, else T0 bit for bit.  stats [n][4]: status, iterations run, inliers of
+ *   the first and of the last iteration.  residuals [n][2]: their rms point-to-plane residuals in
+ *   metres.  normal_eq [n][28]: the upper triangle of J J^T row-major (21), -J r (6) and sum r^2 of
+ *   the last executed iteration.
+ * tslam_tsdf_align_buffers: the device pointers of world_T_cam and stats (either may be NULL).
+ * tslam_tsdf_integrate_aligned: n_frames (at most the last tslam_tsdf_align call's) depth images,
+ *   with BGR colour or NULL, into the volume on the poses of that call; every frame but an UNUSED
+ *   one is integrated.  Follows the rolling window as the other integrate calls do. */
+#define TSLAM_ALIGN_OK 0
+#define TSLAM_ALIGN_UNUSED 1       /* a NaN host pose or an untracked batch frame */
+#define TSLAM_ALIGN_NO_MODEL 2     /* fewer than min_inliers correspondences (an empty map) */
+#define TSLAM_ALIGN_DEGENERATE 3   /* a pivot of the 6 x 6 system <= min_pivot * its largest diagonal entry */
+#define TSLAM_ALIGN_REJECTED 4     /* the total correction exceeds max_translation or max_rotation */
+typedef struct {
+    int32_t iterations, min_inliers;
+    double max_distance;   /* metres between a point and its model vertex */
+    double min_weight, max_depth, step_scale;   /* of the model view, as tslam_tsdf_render_params */
+    double max_translation, max_rotation;       /* metres, radians: the largest total correction */
+    double eps_translation, eps_rotation;       /* a step below both ends the iterations */
+    double min_pivot;
+    int32_t reserved[4];   /* 0 */
+} tslam_tsdf_align_params;
+int tslam_tsdf_align_init(tslam_handle* h, int pair, int rect, const tslam_tsdf_align_params* params, int max_frames);
+int tslam_tsdf_align(tslam_handle* h, const void* depth, int64_t stride_bytes, int n_frames, int64_t first_frame,
+                     const double* world_T_cam, void* stream);
+int tslam_tsdf_align_read(tslam_handle* h, int max_frames, double* world_T_cam, int32_t* stats, double* residuals,
+                          double* normal_eq);
+int tslam_tsdf_align_buffers(tslam_handle* h, void** world_T_cam, void** stats);
+int tslam_tsdf_integrate_aligned(tslam_handle* h, const void* color, const void* depth, int64_t stride_bytes, int n_frames,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

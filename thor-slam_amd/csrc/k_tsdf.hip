@@ -386,6 +386,15 @@ void launch_tsdf(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev
     hipLaunchKernelGGL(k_tsdf_integrate<false>, dim3((unsigned)((int64_t)nbx * nby * nbz)), dim3(256), 0, s, b, nbx, nby);
 }
 
+void launch_tsdf_posed(const TsdfArgs& a, double* poses, hipStream_t s, const TsdfFollowCall* follow) {
+    tsdf_follow_call(follow, poses, a, s);
+    TsdfArgs b = a;
+    b.poses = poses;
+    const int nbx = (a.nx + TSDF_BX - 1) / TSDF_BX, nby = (a.ny + TSDF_BY - 1) / TSDF_BY,
+              nbz = (a.nz + TSDF_BZ - 1) / TSDF_BZ;
+    hipLaunchKernelGGL(k_tsdf_integrate<false>, dim3((unsigned)((int64_t)nbx * nby * nbz)), dim3(256), 0, s, b, nbx, nby);
+}
+
 void launch_tsdf_rig(const BatchCtx& c, uint64_t pairs, int f0, const double* host_wTb_dev, const TsdfRigArgs& a,
                      double* poses, hipStream_t s, const TsdfFollowCall* follow) {
     hipLaunchKernelGGL(k_tsdf_rig_poses, dim3((a.n + 63) / 64), dim3(64), 0, s, c, pairs, a.n_cams, f0, host_wTb_dev, a.n, poses);

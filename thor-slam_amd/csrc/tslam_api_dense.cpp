@@ -90,6 +90,20 @@ int dense_reset(tslam_handle* h) {
     return TSLAM_OK;
 }
 
+// the align state's buffers go back to the device (tslam_tsdf_align_init with NULL; a new volume)
+static void align_off(tslam_handle* h) {
+    for (void** p : {(void**)&h->d_aln_L, (void**)&h->d_aln_poses, (void**)&h->d_aln_wTc_in, (void**)&h->d_aln_depth_m,
+                     (void**)&h->d_aln_normal, (void**)&h->d_aln_state, (void**)&h->d_aln_part, (void**)&h->d_aln_wTc,
+                     (void**)&h->d_aln_stats, (void**)&h->d_aln_resid, (void**)&h->d_aln_neq}) {
+        if (!*p) continue;
+        (void)hipFree(*p);
+        h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), *p), h->allocs.end());
+        *p = nullptr;
+    }
+    h->aln_on = false;
+    h->aln_frames = h->aln_n = 0;
+}
+
 extern "C" {
 
 // -- RGB-D dense mapping: TSDF integration -------------------------------------------------------
@@ -115,6 +129,7 @@ int tslam_tsdf_init(tslam_handle* h, const double* origin, const int32_t* dims, 
     if (rc != TSLAM_OK) return rc;
     if (h->d_tsdf_win) HIPCHK(hipMemset(h->d_tsdf_win, 0, sizeof(TsdfWindow)));   // a new volume: shift 0, not following
     h->tsdf_follow_on = false;
+    align_off(h);   // the align state belongs to the volume it was made for
     a.nx = dims[0];
     a.ny = dims[1];
     a.nz = dims[2];
@@ -474,6 +489,226 @@ int tslam_tsdf_render_read(tslam_handle* h, int view, float* depth_m, uint16_t* 
     if (depth_mm) HIPCHK(hipMemcpy(depth_mm, h->d_rnd_depth_mm + px * view, 2 * px, hipMemcpyDeviceToHost));
     if (normal) HIPCHK(hipMemcpy(normal, h->d_rnd_normal + 3 * px * view, 12 * px, hipMemcpyDeviceToHost));
     if (color) HIPCHK(hipMemcpy(color, h->d_rnd_color + 3 * px * view, 3 * px, hipMemcpyDeviceToHost));
+    return TSLAM_OK;
+}
+
+// -- dense frame-to-model alignment (k_tsdf_align.hip; thor_slam_amd/dense_align.py) ---------------
+int tslam_tsdf_align_init(tslam_handle* h, int pair, int rect, const tslam_tsdf_align_params* params, int max_frames) {
+    if (!h) return fail(TSLAM_EINVAL, "null handle");
+    BA_FLUSH(h);
+    if (!h->tsdf_on) return fail(TSLAM_ESTATE, "no TSDF volume (tslam_tsdf_init)");
+    if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_tsdf_align_init inside a batch");
+    if (!params) {   // off: the buffers go back
+        if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
+        align_off(h);
+        return TSLAM_OK;
+    }
+    if (pair < 0 || pair >= h->P) return fail(TSLAM_EINVAL, "bad pair");
+    const tslam_tsdf_align_params p = *params;
+    if (h->tsdf.nx < 2 || h->tsdf.ny < 2 || h->tsdf.nz < 2) return fail(TSLAM_EINVAL, "alignment needs volume dims >= 2");
+    if (p.iterations < 1 || p.iterations > 64) return fail(TSLAM_EINVAL, "iterations must be 1..64");
+    if (p.min_inliers < 6) return fail(TSLAM_EINVAL, "min_inliers must be >= 6");
+    if (max_frames < 1 || max_frames > TSDF_MAX_FRAMES) return fail(TSLAM_EINVAL, "max_frames must be 1..256");
+    for (const double v : {p.max_distance, p.min_weight, p.max_depth, p.step_scale, p.max_translation, p.max_rotation,
+                           p.eps_translation, p.eps_rotation, p.min_pivot})
+        if (!std::isfinite(v)) return fail(TSLAM_EINVAL, "align parameters must be finite");
+    if (!(p.max_distance > 0.0 && p.max_depth > 0.0 && p.max_translation > 0.0))
+        return fail(TSLAM_EINVAL, "max_distance, max_depth and max_translation must be > 0");
+    if (!(p.min_weight >= 0.0)) return fail(TSLAM_EINVAL, "min_weight must be >= 0");
+    if (!(p.step_scale > 0.0 && p.step_scale <= 1.0)) return fail(TSLAM_EINVAL, "step_scale must be in (0, 1]");
+    if (!(p.max_rotation > 0.0 && p.max_rotation <= 3.141592653589793)) return fail(TSLAM_EINVAL, "max_rotation must be in (0, pi]");
+    if (!(p.eps_translation >= 0.0 && p.eps_rotation >= 0.0)) return fail(TSLAM_EINVAL, "eps_translation and eps_rotation must be >= 0");
+    if (!(p.min_pivot > 0.0 && p.min_pivot < 1.0)) return fail(TSLAM_EINVAL, "min_pivot must be in (0, 1)");
+    for (const int32_t r : p.reserved)
+        if (r != 0) return fail(TSLAM_EINVAL, "reserved must be 0");
+    if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
+    h->aln_on = false;
+    // the pair's rectified camera: rule 1's L on the host, as tslam_tsdf_render_init builds it
+    const int W = h->W, H = h->H;
+    const PairCalib& k = h->calib[pair];
+    const size_t px = (size_t)W * H;
+    std::vector<double> L(px);
+    for (int y = 0; y < H; ++y) {
+        const double dc1 = ((double)y - k.cy) / k.fy;
+        for (int x = 0; x < W; ++x) {
+            const double dc0 = ((double)x - k.cx) / k.fx;
+            L[(size_t)y * W + x] = std::sqrt((dc0 * dc0 + dc1 * dc1) + 1.0);
+        }
+    }
+    const int blocks = ((W + 15) / 16) * ((H + 15) / 16);
+    int pblocks = 256;
+    while (pblocks < blocks) pblocks *= 2;
+    const size_t n = (size_t)max_frames;
+    int rc = dev_grow(h, (void**)&h->d_aln_L, sizeof(double) * px);
+    if (rc == TSLAM_OK && !h->d_aln_poses) rc = dev_alloc(h, (void**)&h->d_aln_poses, sizeof(double) * TSDF_MAX_FRAMES * TSDF_POSE);
+    if (rc == TSLAM_OK && !h->d_aln_wTc_in) rc = dev_alloc(h, (void**)&h->d_aln_wTc_in, sizeof(double) * TSDF_MAX_FRAMES * 16);
+    if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&h->d_aln_depth_m, sizeof(float) * px * n);
+    if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&h->d_aln_normal, sizeof(float) * 3 * px * n);
+    if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&h->d_aln_state, sizeof(double) * ALIGN_STATE * n);
+    if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&h->d_aln_part, sizeof(double) * ALIGN_PART * pblocks * n);   // zeroed: the padding stays zero
+    if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&h->d_aln_wTc, sizeof(double) * 16 * n);
+    if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&h->d_aln_stats, sizeof(int32_t) * ALIGN_STATS * n);
+    if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&h->d_aln_resid, sizeof(double) * 2 * n);
+    if (rc == TSLAM_OK) rc = dev_grow(h, (void**)&h->d_aln_neq, sizeof(double) * 28 * n);
+    if (rc != TSLAM_OK) {
+        align_off(h);
+        return rc;
+    }
+    HIPCHK(hipMemcpy(h->d_aln_L, L.data(), sizeof(double) * px, hipMemcpyHostToDevice));
+    h->aln_prm = p;
+    h->aln_pair = pair;
+    h->aln_rect = rect != 0;
+    h->aln_frames = max_frames;
+    h->aln_pblocks = pblocks;
+    h->aln_n = 0;
+    h->aln_on = true;
+    return TSLAM_OK;
+}
+
+int tslam_tsdf_align(tslam_handle* h, const void* depth, int64_t stride_bytes, int n_frames, int64_t first_frame,
+                     const double* world_T_cam, void* stream) {
+    if (!h) return fail(TSLAM_EINVAL, "null handle");
+    BA_FLUSH(h);
+    if (!h->tsdf_on) return fail(TSLAM_ESTATE, "no TSDF volume (tslam_tsdf_init)");
+    if (!h->aln_on) return fail(TSLAM_ESTATE, "no align state (tslam_tsdf_align_init)");
+    if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_tsdf_align inside a batch");
+    if (!depth || (n_frames > 1 && stride_bytes < 2LL * h->W * h->H)) return fail(TSLAM_EINVAL, "bad depth / stride");
+    if (n_frames < 0 || n_frames > h->aln_frames) return fail(TSLAM_EINVAL, "n_frames must be 0..max_frames");
+    const int pair = h->aln_pair;
+    int f0 = 0;
+    if (!world_T_cam) {   // device poses: frames of the last batch
+        f0 = (int)(first_frame - h->cur_g0);
+        if (first_frame < h->cur_g0 || f0 + n_frames > h->cur_n)
+            return fail(TSLAM_EINVAL, "device poses: frames must belong to the last batch");
+    }
+    h->aln_n = n_frames;
+    if (n_frames == 0) return TSLAM_OK;
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = stream ? (hipStream_t)stream : h->last_stream;
+    const BatchCtx c = make_ctx(h);
+    const TsdfArgs& t = h->tsdf;
+    const tslam_tsdf_align_params& p = h->aln_prm;
+    const PairCalib& k = h->calib[pair];
+    TsdfRenderArgs r{};   // the ray caster as it stands, into this state's images (depth_m and normals only)
+    r.tsdf = t.tsdf;
+    r.weight = t.weight;
+    r.nx = t.nx;
+    r.ny = t.ny;
+    r.nz = t.nz;
+    r.ox = t.ox;
+    r.oy = t.oy;
+    r.oz = t.oz;
+    r.s = t.s;
+    r.win = h->d_tsdf_win;
+    r.W = h->W;
+    r.H = h->H;
+    r.fx = k.fx;
+    r.fy = k.fy;
+    r.cx = k.cx;
+    r.cy = k.cy;
+    r.min_weight = p.min_weight;
+    r.min_depth = 0.0;
+    r.max_depth = p.max_depth;
+    r.step_scale = p.step_scale;
+    r.L = h->d_aln_L;
+    r.depth_m = h->d_aln_depth_m;
+    r.normal = h->d_aln_normal;
+    TsdfAlignArgs a{};
+    a.depth = static_cast<const uint8_t*>(depth);
+    a.stride = stride_bytes;
+    a.n = n_frames;
+    a.W = h->W;
+    a.H = h->H;
+    a.fx = k.fx;
+    a.fy = k.fy;
+    a.cx = k.cx;
+    a.cy = k.cy;
+    const int cam = c.cpp * pair;
+    a.map = (!h->aln_rect && ((h->map_mask >> cam) & 1u)) ? h->d_maps + (size_t)cam * h->W * h->H * 2 : nullptr;
+    a.max_dist = t.max_dist;
+    a.depth_m = h->d_aln_depth_m;
+    a.normal = h->d_aln_normal;
+    a.max_distance2 = p.max_distance * p.max_distance;
+    a.eps_t2 = p.eps_translation * p.eps_translation;
+    a.eps_r2 = p.eps_rotation * p.eps_rotation;
+    a.max_t2 = p.max_translation * p.max_translation;
+    a.rot_lim = 1.0 + 2.0 * std::cos(p.max_rotation);
+    a.min_pivot = p.min_pivot;
+    a.min_inliers = p.min_inliers;
+    a.iterations = p.iterations;
+    a.pblocks = h->aln_pblocks;
+    a.state = h->d_aln_state;
+    a.partial = h->d_aln_part;
+    a.wTc = h->d_aln_wTc;
+    a.stats = h->d_aln_stats;
+    a.resid = h->d_aln_resid;
+    a.neq = h->d_aln_neq;
+    const double* wtc = nullptr;
+    if (world_T_cam) {   // staged on the stream, as tslam_tsdf_render stages its host poses
+        HIPCHK(hipMemcpyAsync(h->d_aln_wTc_in, world_T_cam, sizeof(double) * 16 * n_frames, hipMemcpyHostToDevice, s));
+        wtc = h->d_aln_wTc_in;
+    }
+    launch_tsdf_align(c, pair, f0, wtc, r, a, h->d_aln_poses, s);
+    HIPCHK(hipGetLastError());
+    return TSLAM_OK;
+}
+
+int tslam_tsdf_align_read(tslam_handle* h, int max_frames, double* world_T_cam, int32_t* stats, double* residuals,
+                          double* normal_eq) {
+    if (!h) return fail(TSLAM_EINVAL, "null handle");
+    if (!h->aln_on) return fail(TSLAM_ESTATE, "no align state (tslam_tsdf_align_init)");
+    if (max_frames < 0) return fail(TSLAM_EINVAL, "max_frames must be >= 0");
+    BA_FLUSH(h);
+    if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
+    const size_t n = (size_t)std::min(max_frames, h->aln_n);
+    if (n == 0) return TSLAM_OK;
+    if (world_T_cam) HIPCHK(hipMemcpy(world_T_cam, h->d_aln_wTc, sizeof(double) * 16 * n, hipMemcpyDeviceToHost));
+    if (stats) HIPCHK(hipMemcpy(stats, h->d_aln_stats, sizeof(int32_t) * ALIGN_STATS * n, hipMemcpyDeviceToHost));
+    if (residuals) HIPCHK(hipMemcpy(residuals, h->d_aln_resid, sizeof(double) * 2 * n, hipMemcpyDeviceToHost));
+    if (normal_eq) HIPCHK(hipMemcpy(normal_eq, h->d_aln_neq, sizeof(double) * 28 * n, hipMemcpyDeviceToHost));
+    return TSLAM_OK;
+}
+
+int tslam_tsdf_align_buffers(tslam_handle* h, void** world_T_cam, void** stats) {
+    if (!h) return fail(TSLAM_EINVAL, "null handle");
+    if (!h->aln_on) return fail(TSLAM_ESTATE, "no align state (tslam_tsdf_align_init)");
+    if (world_T_cam) *world_T_cam = h->d_aln_wTc;
+    if (stats) *stats = h->d_aln_stats;
+    return TSLAM_OK;
+}
+
+int tslam_tsdf_integrate_aligned(tslam_handle* h, const void* color, const void* depth, int64_t stride_bytes, int n_frames,
+                                 void* stream) {
+    if (!h) return fail(TSLAM_EINVAL, "null handle");
+    BA_FLUSH(h);
+    if (!h->tsdf_on) return fail(TSLAM_ESTATE, "no TSDF volume (tslam_tsdf_init)");
+    if (!h->aln_on) return fail(TSLAM_ESTATE, "no align state (tslam_tsdf_align_init)");
+    if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_tsdf_integrate_aligned inside a batch");
+    if (color && !h->tsdf_color) return fail(TSLAM_ESTATE, "no colour layer (tslam_tsdf_color before tslam_tsdf_init)");
+    if (!depth || (n_frames > 1 && stride_bytes < 2LL * h->W * h->H)) return fail(TSLAM_EINVAL, "bad depth / stride");
+    if (n_frames < 0 || n_frames > h->aln_n) return fail(TSLAM_EINVAL, "n_frames must be 0 .. the frames of the last tslam_tsdf_align");
+    if (n_frames == 0) return TSLAM_OK;
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = stream ? (hipStream_t)stream : h->last_stream;
+    const int pair = h->aln_pair, cam = make_ctx(h).cpp * pair;
+    TsdfArgs a = h->tsdf;
+    a.W = h->W;
+    a.H = h->H;
+    a.fx = h->calib[pair].fx;
+    a.fy = h->calib[pair].fy;
+    a.cx = h->calib[pair].cx;
+    a.cy = h->calib[pair].cy;
+    a.map = (!h->aln_rect && ((h->map_mask >> cam) & 1u)) ? h->d_maps + (size_t)cam * h->W * h->H * 2 : nullptr;
+    a.stride = stride_bytes;
+    a.win = h->d_tsdf_win;
+    const TsdfFollowCall fc{h->tsdf_follow, h->tsdf_follow_on ? window_layers(h) : TsdfLayers{}, h->d_tsdf_win};
+    if (!color) a.col = a.col_w = nullptr;   // the colour layer keeps its state without colour input
+    a.n = n_frames;   // at most TSDF_MAX_FRAMES: one chunk
+    a.depth = static_cast<const uint8_t*>(depth);
+    a.color = static_cast<const uint8_t*>(color);
+    launch_align_poses(h->d_aln_wTc, h->d_aln_stats, n_frames, h->d_tsdf_poses, s);
+    launch_tsdf_posed(a, h->d_tsdf_poses, s, h->tsdf_follow_on ? &fc : nullptr);
+    HIPCHK(hipGetLastError());
     return TSLAM_OK;
 }
 

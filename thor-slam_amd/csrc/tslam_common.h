@@ -388,6 +388,41 @@ struct TsdfRenderArgs {
 // pair, f0, host_wTc_dev as launch_tsdf; poses: the call's table, written by its pose kernel
 void launch_tsdf_render(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev, const TsdfRenderArgs& a, int n_views,
                         double* poses, hipStream_t s);
+// Dense frame-to-model alignment (k_tsdf_align.hip; thor_slam_amd/dense_align.py): n frames of one
+// camera against the model images rendered at their initial poses.
+#define ALIGN_TERMS 29   // J J^T upper (21), -J r (6), sum r^2, inliers
+#define ALIGN_PART 32    // doubles per block partial
+#define ALIGN_STATE 32   // doubles per frame: T = R rows (9), C (3); T0 alike (12); the active flag [24]
+#define ALIGN_STATS 4    // status, iterations run, inliers of the first and of the last iteration
+struct TsdfAlignArgs {
+    const uint8_t* depth;      // frame 0's depth (u16 mm), frames `stride` bytes apart
+    int64_t stride;
+    int n;                     // frames
+    int W, H;
+    double fx, fy, cx, cy;
+    const int32_t* map;        // as TsdfArgs::map
+    double max_dist;           // the volume's
+    const float* depth_m;      // the model images at T0: [n][H][W] and [n][H][W][3]
+    const float* normal;
+    const double* poses;       // the render's table at T0 [n][TSDF_POSE]
+    double max_distance2, eps_t2, eps_r2, max_t2, rot_lim, min_pivot;   // squares; rot_lim = 1 + 2 cos(max_rotation)
+    int min_inliers, iterations;
+    int pblocks;               // blocks of a view padded to a power of two >= 256
+    double* state;             // [n][ALIGN_STATE]
+    double* partial;           // [n][pblocks][ALIGN_PART]; blocks past the view's stay zero
+    double* wTc;               // out: world_T_cam [n][16]
+    int32_t* stats;            // out: [n][ALIGN_STATS]
+    double* resid;             // out: rms of the first and of the last iteration [n][2]
+    double* neq;               // out: the 28 sums of the last executed iteration [n][28]
+};
+// the render at T0 (r: the align state's own images and ray-length table; pair, f0, host_wTc_dev
+// and poses as launch_tsdf_render), then a.iterations x (accumulate, solve)
+void launch_tsdf_align(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev, const TsdfRenderArgs& r,
+                       const TsdfAlignArgs& a, double* poses, hipStream_t s);
+// the aligned poses as the integrator's table
+void launch_align_poses(const double* wTc, const int32_t* stats, int n, double* out, hipStream_t s);
+// launch_tsdf without its pose kernel: the table `poses` [a.n][TSDF_POSE] is already on the stream
+void launch_tsdf_posed(const TsdfArgs& a, double* poses, hipStream_t s, const TsdfFollowCall* follow = nullptr);
 // dense stereo depth (k_stereo_depth.hip): n frames of one rectified pair -> disp32 (1/32 px) and
 // depth (mm), u16 [n][H][W]; win_left / win_right: u8 [n][H][W] winner maps between its two kernels
 struct StereoDepthArgs {

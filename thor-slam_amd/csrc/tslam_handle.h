@@ -268,6 +268,23 @@ struct tslam_handle {
     uint16_t* d_rnd_depth_mm = nullptr;
     float* d_rnd_normal = nullptr;
     uint8_t* d_rnd_color = nullptr;
+    // dense frame-to-model alignment (tslam_tsdf_align_*): parameters, the pair's ray-length table,
+    // the model images [aln_frames][H][W] of its own render, the per-frame state and block partials,
+    // and the outputs; aln_n: the frames of the last tslam_tsdf_align call
+    bool aln_on = false;
+    tslam_tsdf_align_params aln_prm{};
+    int aln_pair = 0, aln_rect = 0, aln_frames = 0, aln_n = 0, aln_pblocks = 0;
+    double* d_aln_L = nullptr;        // [H][W]
+    double* d_aln_poses = nullptr;    // [TSDF_MAX_FRAMES][TSDF_POSE]: the render's table at T0
+    double* d_aln_wTc_in = nullptr;   // [TSDF_MAX_FRAMES][16] host poses staged
+    float* d_aln_depth_m = nullptr;
+    float* d_aln_normal = nullptr;
+    double* d_aln_state = nullptr;    // [aln_frames][ALIGN_STATE]
+    double* d_aln_part = nullptr;     // [aln_frames][aln_pblocks][ALIGN_PART]
+    double* d_aln_wTc = nullptr;      // [aln_frames][16]
+    int32_t* d_aln_stats = nullptr;   // [aln_frames][ALIGN_STATS]
+    double* d_aln_resid = nullptr;    // [aln_frames][2]
+    double* d_aln_neq = nullptr;      // [aln_frames][28]
     // dense stereo depth (tslam_stereo_depth_*): parameters, output slots and winner-map scratch
     bool sd_on = false;
     tslam_stereo_depth_params sd_prm{};

@@ -134,6 +134,16 @@ class TsdfRenderParams(ctypes.Structure):
     ]
 
 
+class TsdfAlignParams(ctypes.Structure):
+    """tslam_tsdf_align_params: the rule of ``Handle.tsdf_align`` (thor_slam_amd/dense_align.py)."""
+    _fields_ = [
+        ("iterations", ctypes.c_int32), ("min_inliers", ctypes.c_int32), ("max_distance", ctypes.c_double),
+        ("min_weight", ctypes.c_double), ("max_depth", ctypes.c_double), ("step_scale", ctypes.c_double),
+        ("max_translation", ctypes.c_double), ("max_rotation", ctypes.c_double), ("eps_translation", ctypes.c_double),
+        ("eps_rotation", ctypes.c_double), ("min_pivot", ctypes.c_double), ("reserved", ctypes.c_int32 * 4),
+    ]
+
+
 def camera_desc(cam) -> CameraDesc:
     """A ``CameraConfig`` (intrinsics + world extrinsics) as a ``tslam_camera_desc``."""
     d = CameraDesc()
@@ -325,6 +335,15 @@ _SIGNATURES = {
                                                  ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
     "tslam_tsdf_render_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.c_void_p]),
+    "tslam_tsdf_align_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]),
+    "tslam_tsdf_align": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                        ctypes.c_void_p, ctypes.c_void_p]),
+    "tslam_tsdf_align_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p]),
+    "tslam_tsdf_align_buffers": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
+                                                ctypes.POINTER(ctypes.c_void_p)]),
+    "tslam_tsdf_integrate_aligned": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                    ctypes.c_int, ctypes.c_void_p]),
 }
 
 
@@ -1037,6 +1056,66 @@ class Handle:
         _check(self.lib.tslam_tsdf_render_read(self.h, int(view), *[out[k].ctypes.data if k in out else None
                                                                     for k, _, _, _ in spec]))
         return out
+
+    # -- dense frame-to-model alignment (thor_slam_amd/dense_align.py) ---------------------------
+    def tsdf_align_init(self, pair: int = 0, rect: bool = False, max_frames: int = 1, enable: bool = True, **params) -> None:
+        """The camera (``pair``; ``rect``: the depth is the rectified camera's), the most frames of
+        one ``tsdf_align`` call and the rule's parameters (``dense_align.DEFAULTS``); after
+        ``tsdf_init``.  ``enable`` False frees the state."""
+        from .dense_align import DEFAULTS
+
+        if not enable:
+            _check(self.lib.tslam_tsdf_align_init(self.h, 0, 0, None, 0))
+            return
+        unknown = set(params) - set(DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown align parameters {sorted(unknown)}")
+        p = {**DEFAULTS, **params}
+        prm = TsdfAlignParams(int(p["iterations"]), int(p["min_inliers"]), float(p["max_distance"]), float(p["min_weight"]),
+                              float(p["max_depth"]), float(p["step_scale"]), float(p["max_translation"]),
+                              float(p["max_rotation"]), float(p["eps_translation"]), float(p["eps_rotation"]),
+                              float(p["min_pivot"]), (ctypes.c_int32 * 4)())
+        _check(self.lib.tslam_tsdf_align_init(self.h, int(pair), int(bool(rect)), ctypes.addressof(prm), int(max_frames)))
+
+    def tsdf_align(self, depth_dev_ptr: int, stride_bytes: int, n_frames: int, first_frame: int = 0,
+                   world_T_cam: np.ndarray | None = None, stream: int = 0) -> None:
+        """Align n depth frames (device u16 mm, ``stride_bytes`` apart) to the map on the stream
+        (asynchronous), from the host poses world_T_cam [n][4][4] (volume frame) or, with None, from
+        the last batch's tracked device poses of frames first_frame.. ."""
+        poses = None
+        if world_T_cam is not None:
+            poses = np.ascontiguousarray(np.asarray(world_T_cam, dtype=np.float64).reshape(-1, 4, 4))
+        self._align_poses = poses   # stays alive behind the asynchronous call
+        _check(self.lib.tslam_tsdf_align(self.h, ctypes.c_void_p(depth_dev_ptr), int(stride_bytes), int(n_frames),
+                                         int(first_frame), None if poses is None else poses.ctypes.data,
+                                         ctypes.c_void_p(stream)))
+        self._align_n = int(n_frames)
+
+    def tsdf_align_read(self, n_frames: int | None = None) -> dict:
+        """The last ``tsdf_align`` call's results (synchronises): ``world_T_cam`` f64 [n][4][4] (the
+        aligned pose where the status is 0, else the initial pose), ``stats`` i32 [n][4] (status,
+        iterations run, inliers of the first and of the last iteration), ``residuals`` f64 [n][2]
+        (their rms residuals, metres), ``normal_eq`` f64 [n][28]."""
+        n = getattr(self, "_align_n", 0) if n_frames is None else int(n_frames)
+        out = {"world_T_cam": np.zeros((n, 4, 4)), "stats": np.zeros((n, 4), np.int32), "residuals": np.zeros((n, 2)),
+               "normal_eq": np.zeros((n, 28))}
+        _check(self.lib.tslam_tsdf_align_read(self.h, n, *[out[k].ctypes.data for k in ("world_T_cam", "stats", "residuals",
+                                                                                         "normal_eq")]))
+        return out
+
+    def tsdf_align_buffers(self) -> dict:
+        """Device pointers of ``world_T_cam`` (f64 [max_frames][16]) and ``stats`` (i32 [max_frames][4])."""
+        a, b = ctypes.c_void_p(), ctypes.c_void_p()
+        _check(self.lib.tslam_tsdf_align_buffers(self.h, ctypes.byref(a), ctypes.byref(b)))
+        return {"world_T_cam": int(a.value or 0), "stats": int(b.value or 0)}
+
+    def tsdf_integrate_aligned(self, depth_dev_ptr: int, stride_bytes: int, n_frames: int, color_dev_ptr: int | None = None,
+                               stream: int = 0) -> None:
+        """``tsdf_integrate`` (with ``color_dev_ptr``: ``tsdf_integrate_rgbd``) of n frames on the
+        poses of the last ``tsdf_align`` call, which stay on the device."""
+        _check(self.lib.tslam_tsdf_integrate_aligned(self.h, ctypes.c_void_p(color_dev_ptr) if color_dev_ptr else None,
+                                                     ctypes.c_void_p(depth_dev_ptr), int(stride_bytes), int(n_frames),
+                                                     ctypes.c_void_p(stream)))
 
     # -- dense stereo depth (thor_slam_amd/stereo_depth.py) ------------------------------------
     def stereo_depth_init(self, max_frames: int = 1, n_disp: int = 0, uniqueness: int = 10, lr_tol: int = 1) -> None:

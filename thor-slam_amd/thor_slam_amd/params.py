@@ -10,6 +10,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 
+from .dense_align import DEFAULTS as ALIGN_DEFAULTS, check_align_params
 from .dense_follow import check_follow_params
 from .dense_rig import DenseCamerasError
 from .slam.interface import SlamConfig
@@ -166,6 +167,17 @@ class HipSlamConfig(SlamConfig):
     # is observed from mesh_integrator_min_weight on, as the mesh's cubes are
     dense_view_step_scale: float = 0.5
     dense_view_max_distance_m: float | None = None
+    # dense frame-to-model alignment (thor_slam_amd/dense_align.py): before a batch's depth of pair 0
+    # goes into the volume, every frame is aligned to the ray-cast map by projective point-to-plane
+    # ICP from its tracked pose, and integrated on the aligned pose (on the tracked pose when the
+    # alignment fails or the correction exceeds the limits).  Published poses are not changed.
+    # dense_align_max_distance_m None = two voxels.  Needs dense_map, pair 0 alone and one device.
+    dense_align: bool = False
+    dense_align_iterations: int = 10
+    dense_align_max_distance_m: float | None = None
+    dense_align_min_inliers: int = 200
+    dense_align_max_translation_m: float = 0.1
+    dense_align_max_rotation_rad: float = 0.1
     # dense stereo depth (thor_slam_amd/stereo_depth.py): on a stereo rig, pair 0's depth image is
     # computed on the device from the rectified images (candidate disparities 0 .. max_disparity - 1)
     # and feeds dense_map as an RGB-D camera's depth does (no colour layer: the images are gray, so
@@ -195,6 +207,16 @@ class HipSlamConfig(SlamConfig):
     # an RCCL clique over the devices (one per rank), "copy" = device copies (ranks may share a device)
     devices: tuple = ()
     shard_transport: str = "rccl"
+
+    def dense_align_params(self) -> dict:
+        """The rule's parameters (thor_slam_amd/dense_align.py) that ``dense_align`` runs with: the
+        model view as ``get_dense_view`` renders it, out to the integration distance."""
+        gate = self.dense_align_max_distance_m
+        return {**ALIGN_DEFAULTS, "iterations": self.dense_align_iterations, "min_inliers": self.dense_align_min_inliers,
+                "max_distance": 2.0 * self.voxel_size if gate is None else gate,
+                "min_weight": self.mesh_integrator_min_weight, "max_depth": self.tsdf_integrator_max_integration_distance_m,
+                "step_scale": self.dense_view_step_scale, "max_translation": self.dense_align_max_translation_m,
+                "max_rotation": self.dense_align_max_rotation_rad}
 
     def validate(self) -> None:
         if not 1 <= self.n_levels <= MAX_LEVELS:
@@ -256,6 +278,14 @@ class HipSlamConfig(SlamConfig):
                 # the camera-sharded RGB-D map lives on rank 0, behind the shard driver
                 raise ValueError("dense_follow does not run on a sharded rig (devices)")
             check_follow_params(self.dense_follow_margin, self.dense_follow_step, self.dense_follow_anchor)
+        if self.dense_align:
+            if not self.dense_map:
+                raise ValueError("dense_align needs dense_map=True")
+            if self.dense_cameras:
+                raise ValueError("dense_align does not run with dense_cameras (it aligns pair 0's depth on pair 0's pose)")
+            if self.devices:
+                raise ValueError("dense_align does not run on a sharded rig (devices)")
+            check_align_params(**self.dense_align_params(), max_frames=1)
         if not (self.ba_window == 0 or 2 <= self.ba_window <= 10):
             raise ValueError("ba_window must be 0 (off) or in [2, 10]")
         if self.ba_kf_interval < 1 or self.ba_iters < 1:

@@ -531,6 +531,9 @@ class HipSlamEngine(SlamEngine):
                                        cfg.tsdf_integrator_max_integration_distance_m, cfg.tsdf_max_weight)
                 if cfg.dense_follow:   # the window follows the camera (thor_slam_amd/dense_follow.py)
                     self._handle.tsdf_follow(cfg.dense_follow_anchor, cfg.dense_follow_margin, cfg.dense_follow_step)
+                if cfg.dense_align:   # frame-to-model alignment before integration (thor_slam_amd/dense_align.py)
+                    self._handle.tsdf_align_init(pair=0, rect=bool(cfg.stereo_depth), max_frames=cfg.batch_size,
+                                                 **cfg.dense_align_params())
                 if cfg.stereo_depth:   # a stereo rig: the depth comes from the dense matcher (slots per camera)
                     self._handle.stereo_depth_init(max_frames=cfg.batch_size * max(1, len(self._dense_pairs)),
                                                    uniqueness=cfg.stereo_depth_uniqueness,
@@ -987,7 +990,11 @@ class HipSlamEngine(SlamEngine):
                          for ci, p in enumerate(dense)], m, first_frame=g, stream=stream)
                     continue
                 self._handle.stereo_depth(g, m, pair=0, stream=stream)
-                self._handle.tsdf_integrate_rect(depth_ptr, frame_bytes, m, first_frame=g, pair=0, stream=stream)
+                if self._config.dense_align:   # aligned to the map first, integrated on the aligned poses
+                    self._handle.tsdf_align(depth_ptr, frame_bytes, m, first_frame=g, stream=stream)
+                    self._handle.tsdf_integrate_aligned(depth_ptr, frame_bytes, m, stream=stream)
+                else:
+                    self._handle.tsdf_integrate_rect(depth_ptr, frame_bytes, m, first_frame=g, pair=0, stream=stream)
                 self._sd_last[0] = (m - 1, stamp)
             return
         r = self._rects[0]
@@ -998,6 +1005,11 @@ class HipSlamEngine(SlamEngine):
                 [dict(pair=p, depth=records_ptr + p * 5 * hw + 3 * hw, stride_bytes=stride,
                       color=records_ptr + p * 5 * hw if self._dense_color else None) for p in dense],
                 n, first_frame=self._handle.frames_done - n, stream=stream)
+            return
+        if self._config.dense_align:   # aligned to the map first, integrated on the aligned poses
+            self._handle.tsdf_align(records_ptr + 3 * hw, stride, n, first_frame=self._handle.frames_done - n, stream=stream)
+            self._handle.tsdf_integrate_aligned(records_ptr + 3 * hw, stride, n,
+                                                color_dev_ptr=records_ptr if self._dense_color else None, stream=stream)
             return
         if self._dense_color:   # the record's BGR part with its depth part
             self._handle.tsdf_integrate_rgbd(records_ptr, records_ptr + 3 * hw, stride, n,
@@ -1017,6 +1029,19 @@ class HipSlamEngine(SlamEngine):
             return None
         slot, stamp = self._sd_last[int(pair)]
         return self._handle.stereo_depth_read(slot)[0], stamp
+
+    def get_dense_alignment(self) -> dict | None:
+        """The newest batch's frame-to-model alignment (``dense_align``; the rule is
+        thor_slam_amd/dense_align.py): ``world_T_cam`` f64 [n][4][4], the poses the batch's depth
+        was integrated with, in the volume's frame (the aligned pose where ``stats[:, 0]`` is 0, else
+        the tracked pose); ``stats`` i32 [n][4] (status: 0 ok, 1 unused, 2 no model, 3 degenerate,
+        4 rejected; iterations run; inliers of the first and of the last iteration); ``residuals``
+        f64 [n][2] (their rms point-to-plane residuals, metres); ``normal_eq`` f64 [n][28].  None
+        unless ``dense_align`` is on.  Synchronises."""
+        if not (self._config.dense_map and self._config.dense_align) or self._handle is None:
+            return None
+        self.flush()
+        return self._handle.tsdf_align_read()
 
     def get_dense_map(self) -> dict | None:
         """The TSDF volume (nvblox-shaped): ``tsdf`` / ``weight`` f32 [nz][ny][nx] (metres of
