@@ -42,22 +42,10 @@
 __global__ void k_tsdf_poses(BatchCtx c, int pair, int f0, const double* host_wTc, int n, double* out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const double* T;
-    double use = 1.0;
-    if (host_wTc) {
-        T = host_wTc + 16 * (size_t)i;
-        use = __builtin_isfinite(T[0]) ? 1.0 : 0.0;   // NaN pose: skip the frame
-    } else {
-        const size_t o = (size_t)(f0 + i) * c.P + pair;
-        T = c.pose + o * TS_POSE_DOUBLES + 16;
-        const int st = c.stats[o * TS_STATS_INTS];
-        use = (st == 0 || (st == 2 && c.g0 + f0 + i == 0)) ? 1.0 : 0.0;   // tracked, or the first frame
-    }
+    double use = 1.0;   // 0: the frame is skipped
+    const double* T = call_pose(c, pair, f0, host_wTc, i, &use);
     double* q = out + (size_t)i * TSDF_POSE;
-    for (int r = 0; r < 3; ++r) {
-        for (int k = 0; k < 3; ++k) q[3 * r + k] = T[4 * k + r];   // R^T
-        q[9 + r] = -((T[r] * T[3] + T[4 + r] * T[7]) + T[8 + r] * T[11]);
-    }
+    store_cam_T_world(T, q);
     q[12] = use;
 }
 
@@ -76,17 +64,13 @@ __global__ void k_tsdf_rig_poses(BatchCtx c, uint64_t pairs, int n_cams, int f0,
         use = __builtin_isfinite(Tb[0]) ? 1.0 : 0.0;
     } else {
         Tb = c.rig_pose + (size_t)(f0 + f) * TS_POSE_DOUBLES + 16;
-        const int st = c.rig_stats[(size_t)(f0 + f) * TS_STATS_INTS];
-        use = (st == 0 || (st == 2 && c.g0 + f0 + f == 0)) ? 1.0 : 0.0;
+        use = pose_used(c, c.rig_stats[(size_t)(f0 + f) * TS_STATS_INTS], f0, f);
     }
     double A[16], T[16];
     mul4_fixed(c.rig_Einv, Tb, A);
     mul4_fixed(A, c.rig_E + 16 * pair, T);
     double* q = out + (size_t)v * TSDF_POSE;
-    for (int r = 0; r < 3; ++r) {
-        for (int k = 0; k < 3; ++k) q[3 * r + k] = T[4 * k + r];   // R^T
-        q[9 + r] = -((T[r] * T[3] + T[4 + r] * T[7]) + T[8 + r] * T[11]);
-    }
+    store_cam_T_world(T, q);
     q[12] = use;
 }
 
@@ -369,39 +353,34 @@ void launch_tsdf_move(const TsdfLayers& l, const TsdfWindow* win, hipStream_t s)
     hipLaunchKernelGGL(k_tsdf_move<true>, dim3(blocks), dim3(256), 0, s, l, win);
 }
 
-static void tsdf_follow_call(const TsdfFollowCall* fc, const double* poses, const TsdfArgs& a, hipStream_t s) {
-    if (!fc) return;
-    launch_tsdf_follow(poses, a.n, a, fc->f, fc->win, s);
-    launch_tsdf_move(fc->l, fc->win, s);
+// The table `poses` [a.n][TSDF_POSE] is on the stream: the window's decision and move when the call
+// follows, then one block per brick.  Args: TsdfArgs, or TsdfRigArgs for the rig's kernel.
+template <typename Args>
+static void tsdf_integrate_posed(const Args& a, double* poses, hipStream_t s, const TsdfFollowCall* follow) {
+    if (follow) {
+        launch_tsdf_follow(poses, a.n, a, follow->f, follow->win, s);
+        launch_tsdf_move(follow->l, follow->win, s);
+    }
+    Args b = a;
+    b.poses = poses;
+    const int nbx = (a.nx + TSDF_BX - 1) / TSDF_BX, nby = (a.ny + TSDF_BY - 1) / TSDF_BY,
+              nbz = (a.nz + TSDF_BZ - 1) / TSDF_BZ;
+    constexpr bool RIG = std::is_same_v<Args, TsdfRigArgs>;
+    hipLaunchKernelGGL(k_tsdf_integrate<RIG>, dim3((unsigned)((int64_t)nbx * nby * nbz)), dim3(256), 0, s, b, nbx, nby);
 }
 
 void launch_tsdf(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev, const TsdfArgs& a, double* poses,
                  hipStream_t s, const TsdfFollowCall* follow) {
     hipLaunchKernelGGL(k_tsdf_poses, dim3((a.n + 63) / 64), dim3(64), 0, s, c, pair, f0, host_wTc_dev, a.n, poses);
-    tsdf_follow_call(follow, poses, a, s);
-    TsdfArgs b = a;
-    b.poses = poses;
-    const int nbx = (a.nx + TSDF_BX - 1) / TSDF_BX, nby = (a.ny + TSDF_BY - 1) / TSDF_BY,
-              nbz = (a.nz + TSDF_BZ - 1) / TSDF_BZ;
-    hipLaunchKernelGGL(k_tsdf_integrate<false>, dim3((unsigned)((int64_t)nbx * nby * nbz)), dim3(256), 0, s, b, nbx, nby);
+    tsdf_integrate_posed(a, poses, s, follow);
 }
 
 void launch_tsdf_posed(const TsdfArgs& a, double* poses, hipStream_t s, const TsdfFollowCall* follow) {
-    tsdf_follow_call(follow, poses, a, s);
-    TsdfArgs b = a;
-    b.poses = poses;
-    const int nbx = (a.nx + TSDF_BX - 1) / TSDF_BX, nby = (a.ny + TSDF_BY - 1) / TSDF_BY,
-              nbz = (a.nz + TSDF_BZ - 1) / TSDF_BZ;
-    hipLaunchKernelGGL(k_tsdf_integrate<false>, dim3((unsigned)((int64_t)nbx * nby * nbz)), dim3(256), 0, s, b, nbx, nby);
+    tsdf_integrate_posed(a, poses, s, follow);
 }
 
 void launch_tsdf_rig(const BatchCtx& c, uint64_t pairs, int f0, const double* host_wTb_dev, const TsdfRigArgs& a,
                      double* poses, hipStream_t s, const TsdfFollowCall* follow) {
     hipLaunchKernelGGL(k_tsdf_rig_poses, dim3((a.n + 63) / 64), dim3(64), 0, s, c, pairs, a.n_cams, f0, host_wTb_dev, a.n, poses);
-    tsdf_follow_call(follow, poses, a, s);
-    TsdfRigArgs b = a;
-    b.poses = poses;
-    const int nbx = (a.nx + TSDF_BX - 1) / TSDF_BX, nby = (a.ny + TSDF_BY - 1) / TSDF_BY,
-              nbz = (a.nz + TSDF_BZ - 1) / TSDF_BZ;
-    hipLaunchKernelGGL(k_tsdf_integrate<true>, dim3((unsigned)((int64_t)nbx * nby * nbz)), dim3(256), 0, s, b, nbx, nby);
+    tsdf_integrate_posed(a, poses, s, follow);
 }

@@ -317,10 +317,7 @@ __global__ void k_align_poses(const double* wTc, const int32_t* stats, int n, do
     if (i >= n) return;
     const double* T = wTc + 16 * (size_t)i;
     double* q = out + (size_t)i * TSDF_POSE;
-    for (int r = 0; r < 3; ++r) {
-        for (int k = 0; k < 3; ++k) q[3 * r + k] = T[4 * k + r];   // R^T
-        q[9 + r] = -((T[r] * T[3] + T[4 + r] * T[7]) + T[8 + r] * T[11]);
-    }
+    store_cam_T_world(T, q);
     q[12] = stats[(size_t)i * ALIGN_STATS] != 1 ? 1.0 : 0.0;   // every frame but an UNUSED one
 }
 

@@ -17,17 +17,8 @@
 __global__ void k_render_poses(BatchCtx c, int pair, int f0, const double* host_wTc, int n, double* out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const double* T;
-    double use = 1.0;
-    if (host_wTc) {
-        T = host_wTc + 16 * (size_t)i;
-        use = __builtin_isfinite(T[0]) ? 1.0 : 0.0;   // NaN pose: a zero image
-    } else {
-        const size_t o = (size_t)(f0 + i) * c.P + pair;
-        T = c.pose + o * TS_POSE_DOUBLES + 16;
-        const int st = c.stats[o * TS_STATS_INTS];
-        use = (st == 0 || (st == 2 && c.g0 + f0 + i == 0)) ? 1.0 : 0.0;   // tracked, or the first frame
-    }
+    double use = 1.0;   // 0: a zero image
+    const double* T = call_pose(c, pair, f0, host_wTc, i, &use);
     double* q = out + (size_t)i * TSDF_POSE;
     for (int r = 0; r < 3; ++r) {
         for (int k = 0; k < 3; ++k) q[3 * r + k] = T[4 * r + k];

@@ -1,7 +1,7 @@
 // tslam_api.cpp — the core of the C-ABI of libtslam_hip.so (declared in include/tslam.h): the
 // handle's workspace and lifecycle, the frame pipeline and its stage table, reads, the rig, the
 // motion prior and the asynchronous host boundary.  Local BA, the shard exchange, relocalisation /
-// loop closure and the dense map live in tslam_api_{ba,exchange,loop,dense}.cpp.
+// loop closure and the dense map live in tslam_api_{ba,exchange,loop,tsdf,render,stereo,dense}.cpp.
 //
 // Owns the device workspace of one handle and sequences the stage kernels of a batch on the
 // caller's stream.  The launch functions never allocate, copy synchronously or synchronise, so
@@ -35,15 +35,19 @@ int dev_alloc(tslam_handle* h, void** p, size_t bytes) {
     return TSLAM_OK;
 }
 
+// A buffer back to the device: freed, forgotten by the handle, its pointer null (null: nothing to do)
+void dev_release(tslam_handle* h, void** p) {
+    if (!*p) return;
+    (void)hipFree(*p);
+    h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), *p), h->allocs.end());
+    *p = nullptr;
+}
+
 // The device grow helper: a buffer below `need` bytes (*cap; without `cap`, any buffer) is released
 // and allocated afresh, zeroed, at exactly `need`
 int dev_grow(tslam_handle* h, void** p, size_t need, size_t* cap) {
     if (cap && *cap >= need && *p) return TSLAM_OK;
-    if (*p) {
-        (void)hipFree(*p);
-        h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), *p), h->allocs.end());
-        *p = nullptr;
-    }
+    dev_release(h, p);
     const int rc = dev_alloc(h, p, need);
     if (cap) *cap = rc == TSLAM_OK ? need : 0;
     return rc;

@@ -240,11 +240,7 @@ int tslam_loop_init(tslam_handle* h, int max_keyframes, int signature) {
     if (rc == TSLAM_OK) rc = ensure_reloc_scratch(h);
     if (rc != TSLAM_OK) return rc;
     for (void** p : {(void**)&h->d_lp_snap_kps, (void**)&h->d_lp_snap_kcount, (void**)&h->d_lp_snap_desc})
-        if (*p) {   // snapshots follow the capacity: tslam_loop_auto allocates them again
-            (void)hipFree(*p);
-            h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), *p), h->allocs.end());
-            *p = nullptr;
-        }
+        dev_release(h, p);   // snapshots follow the capacity: tslam_loop_auto allocates them again
     h->lp_auto = 0;
     h->lp_cap = max_keyframes;
     h->lp_S = signature;

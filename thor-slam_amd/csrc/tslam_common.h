@@ -616,6 +616,37 @@ __device__ __forceinline__ bool xcd_image_block(int b, int n_img, int bpi, int* 
     return *img < n_img;
 }
 
+// The use flag of the pose record of frame f0 + i of the batch from its status: tracked, or the
+// global first frame
+__device__ __forceinline__ double pose_used(const BatchCtx& c, int st, int f0, int i) {
+    return (st == 0 || (st == 2 && c.g0 + f0 + i == 0)) ? 1.0 : 0.0;
+}
+
+// The pose of entry i of a call and its use flag: the host's world_T_cam [n][16] (a NaN pose is
+// not used), or T_abs of `pair` at frame f0 + i of the batch with its status' flag.
+__device__ __forceinline__ const double* call_pose(const BatchCtx& c, int pair, int f0, const double* host_wTc, int i,
+                                                   double* use) {
+    if (host_wTc) {
+        const double* T = host_wTc + 16 * (size_t)i;
+        *use = __builtin_isfinite(T[0]) ? 1.0 : 0.0;
+        return T;
+    }
+    const size_t o = (size_t)(f0 + i) * c.P + pair;
+    const double* T = c.pose + o * TS_POSE_DOUBLES + 16;
+    const int st = c.stats[o * TS_STATS_INTS];
+    *use = pose_used(c, st, f0, i);
+    return T;
+}
+
+// world_T_cam T (4 x 4, row-major) inverted into a TSDF_POSE entry: R^T (9) and -R^T t (3), the
+// integrator's cam_T_world; the use flag q[12] is the caller's
+__device__ __forceinline__ void store_cam_T_world(const double* T, double* q) {
+    for (int r = 0; r < 3; ++r) {
+        for (int k = 0; k < 3; ++k) q[3 * r + k] = T[4 * k + r];   // R^T
+        q[9 + r] = -((T[r] * T[3] + T[4 + r] * T[7]) + T[8 + r] * T[11]);
+    }
+}
+
 // Level of y-sorted position `pos` (levels are laid out back to back, koff[l] .. koff[l+1]).
 __device__ __forceinline__ int pos_level(const LevelGeom& g, int pos) {
     int l = 0;

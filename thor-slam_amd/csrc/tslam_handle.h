@@ -241,7 +241,7 @@ struct tslam_handle {
     double *d_pg_H = nullptr, *d_pg_g = nullptr, *d_pg_delta = nullptr, *d_pg_Ld = nullptr;
     int32_t *d_pg_edges = nullptr, *d_pg_adj_off = nullptr, *d_pg_adj = nullptr, *d_pg_ftile = nullptr;
     double* d_pg_cost = nullptr;   // the solve's cost (k_pg_cost_sum), one double
-    // ---- tslam_api_dense.cpp ----
+    // ---- tslam_api_tsdf.cpp ----
     // RGB-D dense mapping (tslam_tsdf_*): dense TSDF volume + per-launch pose scratch
     bool tsdf_on = false;
     bool tsdf_color = false;          // colour layer (tslam_tsdf_color)
@@ -255,6 +255,7 @@ struct tslam_handle {
     TsdfWindow* d_tsdf_win = nullptr; // {shift, delta}, written on the device
     float* d_tsdf_scratch = nullptr;  // the move's copy of every layer (each layer's base a multiple of 4 floats)
     size_t tsdf_scratch_cap = 0;
+    // ---- tslam_api_render.cpp ----
     // the volume seen from a pose (tslam_tsdf_render_*): parameters, the camera's ray-length table,
     // the call's pose table and staged host poses, and the images [rnd_views][H][W] of every
     // output the init asked for (the others stay null)
@@ -285,6 +286,7 @@ struct tslam_handle {
     int32_t* d_aln_stats = nullptr;   // [aln_frames][ALIGN_STATS]
     double* d_aln_resid = nullptr;    // [aln_frames][2]
     double* d_aln_neq = nullptr;      // [aln_frames][28]
+    // ---- tslam_api_stereo.cpp ----
     // dense stereo depth (tslam_stereo_depth_*): parameters, output slots and winner-map scratch
     bool sd_on = false;
     tslam_stereo_depth_params sd_prm{};
@@ -305,6 +307,7 @@ struct tslam_handle {
     tslam_stereo_depth_filter_params sd_flt_prm{};
     uint32_t* d_sd_label = nullptr;   // [sd_frames][H][W], with a speckle size only
     uint32_t* d_sd_count = nullptr;
+    // ---- tslam_api_dense.cpp ----
     // dense-map outputs (tslam_mesh_* / tslam_esdf_*): scratch sized on first use
     uint8_t* d_mesh_cfg = nullptr;    // [cubes] configuration bytes
     uint32_t* d_mesh_bsum = nullptr;  // [blocks] triangle totals
@@ -345,6 +348,7 @@ struct tslam_handle {
 TSLAM_INTERNAL int fail(int code, const std::string& msg);   // sets tslam_last_error(), returns `code`
 TSLAM_INTERNAL int dev_alloc(tslam_handle* h, void** p, size_t bytes);
 TSLAM_INTERNAL int dev_grow(tslam_handle* h, void** p, size_t need, size_t* cap = nullptr);
+TSLAM_INTERNAL void dev_release(tslam_handle* h, void** p);   // hipFree, out of h->allocs, *p = nullptr
 TSLAM_INTERNAL int pinned_reserve(tslam_handle* h, void** p, size_t* cap, size_t bytes);
 TSLAM_INTERNAL BatchCtx make_ctx(tslam_handle* h);
 
@@ -380,5 +384,40 @@ TSLAM_INTERNAL void loop_auto_store(tslam_handle* h, const BatchCtx& c, hipStrea
 TSLAM_INTERNAL int loop_reset(tslam_handle* h);
 TSLAM_INTERNAL void loop_destroy(tslam_handle* h);
 
-// -- tslam_api_dense.cpp ---------------------------------------------------------------------------
+// the stream of a call: the caller's, or the one the handle worked on last
+static inline hipStream_t call_stream(const tslam_handle* h, void* stream) { return stream ? (hipStream_t)stream : h->last_stream; }
+
+// -- tslam_api_tsdf.cpp ----------------------------------------------------------------------------
 TSLAM_INTERNAL int dense_reset(tslam_handle* h);
+TSLAM_INTERNAL size_t tsdf_voxels(const tslam_handle* h);
+TSLAM_INTERNAL int dense_quiesce(tslam_handle* h);   // every stream's work on the map is done
+TSLAM_INTERNAL int no_volume();                      // TSLAM_ESTATE, "no TSDF volume (tslam_tsdf_init)"
+// The checks that open an entry point that works on the volume outside a batch, in the order all of
+// them report: a deferred BA flushed, no volume, `ready` false (`need`: the render or the align state
+// the call works with), "`name` inside a batch".  `h` is not null.
+TSLAM_INTERNAL int dense_open(tslam_handle* h, const char* name, bool ready = true, const char* need = nullptr);
+// device poses (host_poses null): frames first_frame .. first_frame + n - 1 must belong to the last
+// batch, *f0 is the first one's index in it; with host poses nothing is asked and *f0 = 0
+TSLAM_INTERNAL int batch_frames(const tslam_handle* h, const double* host_poses, int64_t first_frame, int n, int* f0);
+// host poses [n][16] copied onto the stream into `staging`, *staged = staging; device poses
+// (host null): nothing is copied and *staged = null
+TSLAM_INTERNAL int stage_poses(const double* host, int n, double* staging, hipStream_t s, const double** staged);
+// the window as the device has it once `s` has drained
+TSLAM_INTERNAL int window_read(tslam_handle* h, hipStream_t s, int32_t shift[3], double origin[3]);
+// a pair's rectified left camera; map: the raw camera's undistortion table, null for depth that is
+// rectified already (`rect`) and for a pair without a table
+struct PairCamera {
+    double fx, fy, cx, cy;
+    const int32_t* map;
+};
+TSLAM_INTERNAL PairCamera pair_camera(tslam_handle* h, int pair, bool rect);
+// what every integrate call hands k_tsdf_integrate but its frames: the volume, the window's record,
+// the camera (its table in `map`; the rig's cameras go into their own records), and the colour layer
+// only with colour input; and what the call's first chunk does while the window follows
+TSLAM_INTERNAL TsdfArgs integrate_args(const tslam_handle* h, const PairCamera& k, bool color_given);
+TSLAM_INTERNAL TsdfFollowCall follow_call(const tslam_handle* h);
+// the fields of a that describe the volume: tsdf, weight, dims, origin, s, win (the colour layer is the caller's)
+TSLAM_INTERNAL void volume_view(const tslam_handle* h, TsdfRenderArgs& a);
+
+// -- tslam_api_render.cpp --------------------------------------------------------------------------
+TSLAM_INTERNAL void align_off(tslam_handle* h);   // the align state belongs to the volume it was made for
