@@ -286,6 +286,18 @@ def test_ba_inertial_factors_parity():
     assert np.abs(want[-1]["bias"][occ][:, 3:6]).max() > 1e-4   # the gyroscope biases moved off zero
 
 
+@functools.lru_cache(maxsize=1)
+def _two_pairs_case(n: int):
+    """Two stereo pairs fed the same frames: pair 0 with IMU rotation + inertial factors, pair 1
+    with other rotation factors only, and each pair's oracle windows (computed once)."""
+    sc, _ = _scenario_and_oracle(n)
+    imu0, imu1 = _imu_factors(sc, n), _imu_factors(sc, n, angle=-2e-3, weight=5e4)
+    ine = _inertial_factors(sc, n)
+    want = (_oracle_windows(sc, imu0, ine), _oracle_windows(sc, imu1))
+    frames = np.ascontiguousarray(np.concatenate([sc["frames"], sc["frames"]], axis=1))   # [n][4][H][W]
+    return sc, imu0, imu1, ine, want, frames
+
+
 def test_ba_two_pairs_own_factors_parity():
     """Two independent stereo pairs (no rig) fed the same frames, each window with its own
     keyframe factors — pair 0 IMU rotation + inertial factors, pair 1 other rotation factors only —
@@ -297,11 +309,7 @@ def test_ba_two_pairs_own_factors_parity():
     from thor_slam_amd._lib import Handle
 
     n, batch = 12, 3
-    sc, _ = _scenario_and_oracle(n)
-    imu0, imu1 = _imu_factors(sc, n), _imu_factors(sc, n, angle=-2e-3, weight=5e4)
-    ine = _inertial_factors(sc, n)
-    want = (_oracle_windows(sc, imu0, ine), _oracle_windows(sc, imu1))
-    frames = np.ascontiguousarray(np.concatenate([sc["frames"], sc["frames"]], axis=1))   # [n][4][H][W]
+    sc, imu0, imu1, ine, want, frames = _two_pairs_case(n)
     dev = torch.from_numpy(frames).cuda()
     h = Handle([sc["rect"], sc["rect"]], sc["cfg"], max_batch=batch)
     try:
@@ -324,6 +332,55 @@ def test_ba_two_pairs_own_factors_parity():
     a0, a1 = want[0][-1], want[1][-1]
     occ = a0["frames"] >= 0
     assert max(rel_frobenius(a0["T_cw"][s_], a1["T_cw"][s_]) for s_ in np.nonzero(occ)[0]) > 1e-7   # the windows differ
+
+
+def test_ba_two_pairs_graph_replay_equals_direct_launches():
+    """Two pair windows without a rig, each keyframe's chains replayed from graphs against the
+    direct launches (the setup of test_ba_two_pairs_own_factors_parity: two evictions, pair 0 with
+    IMU rotation + inertial factors, pair 1 with other rotation factors only).  Both paths issue
+    eviction + solve pair after pair; the pairs share no state.  After every batch both pairs'
+    windows, pair 0's velocities and biases, and the last batch's poses agree bit for bit; the
+    direct run agrees with each pair's oracle window to 1e-9."""
+    import torch
+
+    from thor_slam_amd._lib import Handle
+
+    n, batch = 12, 3
+    sc, imu0, imu1, ine, want, frames = _two_pairs_case(n)
+    dev = torch.from_numpy(frames).cuda()
+    runs = {}
+    for graph in (False, True):
+        h = Handle([sc["rect"], sc["rect"]], sc["cfg"], max_batch=batch)
+        try:
+            h.ba_graph(graph)
+            h.ba_inertial(*INE_CFG, pair=0)
+            for g, (M, w) in imu0.items():
+                h.ba_imu_factor(g, M, w, pair=0)
+            for g, (M, w) in imu1.items():
+                h.ba_imu_factor(g, M, w, pair=1)
+            for g, (f, v0) in ine.items():
+                h.ba_inertial_factor(g, f, v0, pair=0)
+            snaps = []
+            for b0 in range(0, n, batch):
+                h.submit(dev[b0:].data_ptr(), batch, torch.cuda.current_stream().cuda_stream)
+                snaps.append((h.ba_read(0), h.ba_read(1), h.ba_read_inertial(0)))
+            runs[graph] = (snaps, h.read_poses(batch))
+        finally:
+            h.close()
+    for k, (a, b) in enumerate(zip(runs[False][0], runs[True][0])):
+        for p in (0, 1):
+            _compare(a[p], want[p][(k + 1) * batch - 1], f"direct, pair {p}, after frame {(k + 1) * batch - 1}")
+            for key in ("frames", "lm", "T_cw", "X"):
+                np.testing.assert_array_equal(np.asarray(a[p][key]).view(np.uint8), np.asarray(b[p][key]).view(np.uint8),
+                                              err_msg=f"batch {k} pair {p} {key}")
+            assert a[p]["ok"] and b[p]["ok"] and a[p]["n_lm"] == b[p]["n_lm"] > 50
+        wk = want[0][(k + 1) * batch - 1]
+        occ = wk["frames"] >= 0
+        assert np.abs(a[2]["vel"][occ] - wk["vel"][occ]).max() < 1e-9 * np.abs(wk["vel"][occ]).max()
+        for key in ("vel", "bias"):
+            np.testing.assert_array_equal(a[2][key].view(np.uint8), b[2][key].view(np.uint8), err_msg=f"batch {k} {key}")
+    for key, a in runs[False][1].items():   # the last batch's published poses
+        np.testing.assert_array_equal(a, runs[True][1][key], err_msg=key)
 
 
 def test_ba_deferred_issue_equals_immediate():

@@ -67,6 +67,14 @@ __device__ __forceinline__ bool kp_obs(const BatchCtx& c, int slot, int cam, int
 typedef const __attribute__((address_space(4))) BatchCtx* __restrict__ BaCtxRef;
 typedef const __attribute__((address_space(4))) BaArgs* __restrict__ BaArgsRef;
 
+// A kernel of the keyframe chain, defined once: NAME(context, arguments) by value, NAME_rec by record,
+// over the same body (k_ba_schur's pair is written out: `fused` reaches the two differently).
+#define BA_CHAIN_KERNEL(NAME, THREADS, BODY)                                                     \
+    __global__ __launch_bounds__(THREADS) void NAME(BatchCtx c, BaArgs a) { BODY(c, a); }        \
+    __global__ __launch_bounds__(THREADS) void NAME##_rec(BaCtxRef c, BaArgsRef a) {             \
+        BODY(*(const BatchCtx*)c, *(const BaArgs*)a);                                            \
+    }
+
 // ---------------------------------------------------------------------------------------------
 // keyframe insertion (after the batch that contains frame g) and eviction
 // ---------------------------------------------------------------------------------------------
@@ -83,10 +91,7 @@ __device__ __forceinline__ void d_ba_evict_min(const BatchCtx& c, const BaArgs& 
     const int id = q.lm[(size_t)a.order[r] * K + k], lo = a.slot * K;
     if (id >= lo && id < lo + K) atomicMin(&q.remap[id - lo], i);
 }
-__global__ __launch_bounds__(256) void k_ba_evict_min(BatchCtx c, BaArgs a) { d_ba_evict_min(c, a); }
-__global__ __launch_bounds__(256) void k_ba_evict_min_rec(BaCtxRef c, BaArgsRef a) {
-    d_ba_evict_min(*(const BatchCtx*)c, *(const BaArgs*)a);
-}
+BA_CHAIN_KERNEL(k_ba_evict_min, 256, d_ba_evict_min)
 
 __device__ __forceinline__ void d_ba_evict_move(const BatchCtx& c, const BaArgs& a) {
     BA_PRIO;
@@ -107,10 +112,7 @@ __device__ __forceinline__ void d_ba_evict_move(const BatchCtx& c, const BaArgs&
         q.gid[nid] = q.gid[id];
     }
 }
-__global__ __launch_bounds__(256) void k_ba_evict_move(BatchCtx c, BaArgs a) { d_ba_evict_move(c, a); }
-__global__ __launch_bounds__(256) void k_ba_evict_move_rec(BaCtxRef c, BaArgsRef a) {
-    d_ba_evict_move(*(const BatchCtx*)c, *(const BaArgs*)a);
-}
+BA_CHAIN_KERNEL(k_ba_evict_move, 256, d_ba_evict_move)
 
 // ---------------------------------------------------------------------------------------------
 // observation set of a solve (one block): gate at the current estimate, >= 2 observations per
@@ -271,10 +273,7 @@ __device__ __forceinline__ void d_ba_insert_gate(const BatchCtx& c, const BaArgs
     }
     q.keep[i] = (uint8_t)keep;
 }
-__global__ __launch_bounds__(256) void k_ba_insert_gate(BatchCtx c, BaArgs a) { d_ba_insert_gate(c, a); }
-__global__ __launch_bounds__(256) void k_ba_insert_gate_rec(BaCtxRef c, BaArgsRef a) {
-    d_ba_insert_gate(*(const BatchCtx*)c, *(const BaArgs*)a);
-}
+BA_CHAIN_KERNEL(k_ba_insert_gate, 256, d_ba_insert_gate)
 
 // Compaction after the gate, as a deterministic tiled scan (tiles of BA_TILE items):
 //   landmark tiles over the ids (flag: >= 2 gated observations) -> compact index li = rank of the
@@ -373,10 +372,7 @@ __device__ __forceinline__ void d_ba_tilecount(const BatchCtx& c, const BaArgs& 
         q.lpre[blockIdx.x * 64 + threadIdx.x] = x - pc;
     }
 }
-__global__ __launch_bounds__(256) void k_ba_tilecount(BatchCtx c, BaArgs a) { d_ba_tilecount(c, a); }
-__global__ __launch_bounds__(256) void k_ba_tilecount_rec(BaCtxRef c, BaArgsRef a) {
-    d_ba_tilecount(*(const BatchCtx*)c, *(const BaArgs*)a);
-}
+BA_CHAIN_KERNEL(k_ba_tilecount, 256, d_ba_tilecount)
 
 // Scatter after the tile counts; each block takes its tile's offset from the counts of the tiles
 // before it (landmark tiles and observation tiles are scanned separately), and block 0 also
@@ -490,10 +486,7 @@ __device__ __forceinline__ void d_ba_tilescatter(const BatchCtx& c, const BaArgs
             }
     }
 }
-__global__ __launch_bounds__(256) void k_ba_tilescatter(BatchCtx c, BaArgs a) { d_ba_tilescatter(c, a); }
-__global__ __launch_bounds__(256) void k_ba_tilescatter_rec(BaCtxRef c, BaArgsRef a) {
-    d_ba_tilescatter(*(const BatchCtx*)c, *(const BaArgs*)a);
-}
+BA_CHAIN_KERNEL(k_ba_tilescatter, 256, d_ba_tilescatter)
 
 // ---------------------------------------------------------------------------------------------
 // one Gauss-Newton step
@@ -833,8 +826,7 @@ __device__ __forceinline__ void d_ba_schur(const BatchCtx& c, const BaArgs& a, i
     }
 }
 __global__ __launch_bounds__(BA_SCHUR_THREADS) void k_ba_schur(BatchCtx c, BaArgs a) { d_ba_schur(c, a, a.fused_backsub); }
-__global__ __launch_bounds__(BA_SCHUR_THREADS) void k_ba_schur_rec(BaCtxRef c, BaArgsRef a,
-    int fused) {
+__global__ __launch_bounds__(BA_SCHUR_THREADS) void k_ba_schur_rec(BaCtxRef c, BaArgsRef a, int fused) {
     d_ba_schur(*(const BatchCtx*)c, *(const BaArgs*)a, fused);
 }
 
@@ -872,10 +864,7 @@ __device__ __forceinline__ void d_ba_reduce(const BatchCtx& c, const BaArgs& a) 
     if (e < 4096) q.C[e] = v;
     else q.cam_U[e - 4096] = v;
 }
-__global__ __launch_bounds__(64 * BA_SOLVE_WAVES) void k_ba_reduce(BatchCtx c, BaArgs a) { d_ba_reduce(c, a); }
-__global__ __launch_bounds__(64 * BA_SOLVE_WAVES) void k_ba_reduce_rec(BaCtxRef c, BaArgsRef a) {
-    d_ba_reduce(*(const BatchCtx*)c, *(const BaArgs*)a);
-}
+BA_CHAIN_KERNEL(k_ba_reduce, 64 * BA_SOLVE_WAVES, d_ba_reduce)
 
 // Reduced camera system (camera 0 = gauge): S = blockdiag(U + lam) - C, b = -g_c + C[:, 60].
 // Blocked right-looking LDL^T over the 6-wide camera blocks (m = 6 (n - 1) <= 54), one block of
@@ -1443,19 +1432,13 @@ __device__ __forceinline__ void d_ba_solve(const BatchCtx& c, const BaArgs& a) {
     BA_PRIO;
     ba_solve_block<false, false>(c, a);
 }
-__global__ __launch_bounds__(64 * BA_SOLVE_WAVES) void k_ba_solve(BatchCtx c, BaArgs a) { d_ba_solve(c, a); }
-__global__ __launch_bounds__(64 * BA_SOLVE_WAVES) void k_ba_solve_rec(BaCtxRef c, BaArgsRef a) {
-    d_ba_solve(*(const BatchCtx*)c, *(const BaArgs*)a);
-}
+BA_CHAIN_KERNEL(k_ba_solve, 64 * BA_SOLVE_WAVES, d_ba_solve)
 
 __device__ __forceinline__ void d_ba_solve_ine(const BatchCtx& c, const BaArgs& a) {
     BA_PRIO;
     ba_solve_block<false, true>(c, a);
 }
-__global__ __launch_bounds__(64 * BA_SOLVE_WAVES) void k_ba_solve_ine(BatchCtx c, BaArgs a) { d_ba_solve_ine(c, a); }
-__global__ __launch_bounds__(64 * BA_SOLVE_WAVES) void k_ba_solve_ine_rec(BaCtxRef c, BaArgsRef a) {
-    d_ba_solve_ine(*(const BatchCtx*)c, *(const BaArgs*)a);
-}
+BA_CHAIN_KERNEL(k_ba_solve_ine, 64 * BA_SOLVE_WAVES, d_ba_solve_ine)
 
 // k_ba_reduce and k_ba_solve in one launch (a stereo pair's own solve): the reduction's blocks
 // (k_ba_reduce's fixed order, waves 0-3) publish their sums with write-through (agent-scope)
@@ -1488,20 +1471,14 @@ __device__ __forceinline__ void d_ba_reduce_solve(const BatchCtx& c, const BaArg
     BA_PRIO;
     ba_reduce_solve_body<false>(c, a);
 }
-__global__ __launch_bounds__(64 * BA_SOLVE_WAVES) void k_ba_reduce_solve(BatchCtx c, BaArgs a) { d_ba_reduce_solve(c, a); }
-__global__ __launch_bounds__(64 * BA_SOLVE_WAVES) void k_ba_reduce_solve_rec(BaCtxRef c, BaArgsRef a) {
-    d_ba_reduce_solve(*(const BatchCtx*)c, *(const BaArgs*)a);
-}
+BA_CHAIN_KERNEL(k_ba_reduce_solve, 64 * BA_SOLVE_WAVES, d_ba_reduce_solve)
 
 // with the window's inertial factors (velocities + accelerometer bias eliminated into S)
 __device__ __forceinline__ void d_ba_reduce_solve_ine(const BatchCtx& c, const BaArgs& a) {
     BA_PRIO;
     ba_reduce_solve_body<true>(c, a);
 }
-__global__ __launch_bounds__(64 * BA_SOLVE_WAVES) void k_ba_reduce_solve_ine(BatchCtx c, BaArgs a) { d_ba_reduce_solve_ine(c, a); }
-__global__ __launch_bounds__(64 * BA_SOLVE_WAVES) void k_ba_reduce_solve_ine_rec(BaCtxRef c, BaArgsRef a) {
-    d_ba_reduce_solve_ine(*(const BatchCtx*)c, *(const BaArgs*)a);
-}
+BA_CHAIN_KERNEL(k_ba_reduce_solve_ine, 64 * BA_SOLVE_WAVES, d_ba_reduce_solve_ine)
 
 
 // The last iteration's landmark update and the write-back of the window's landmarks: 16 lanes
@@ -1562,10 +1539,7 @@ __device__ __forceinline__ void d_ba_backsub(const BatchCtx& c, const BaArgs& a)
     const int id = q.lm_id[r];
     for (int i = 0; i < 3; ++i) q.X[(size_t)id * 3 + i] = upd ? q.Xc[(size_t)r * 3 + i] + x[i] : q.Xc[(size_t)r * 3 + i];
 }
-__global__ __launch_bounds__(256) void k_ba_backsub(BatchCtx c, BaArgs a) { d_ba_backsub(c, a); }
-__global__ __launch_bounds__(256) void k_ba_backsub_rec(BaCtxRef c, BaArgsRef a) {
-    d_ba_backsub(*(const BatchCtx*)c, *(const BaArgs*)a);
-}
+BA_CHAIN_KERNEL(k_ba_backsub, 256, d_ba_backsub)
 
 // ---------------------------------------------------------------------------------------------
 // host launchers
@@ -1602,61 +1576,120 @@ void launch_ba_kf_assoc(const BatchCtx& c, int32_t* dst, int iv, hipStream_t s) 
     hipLaunchKernelGGL(k_ba_kf_assoc, dim3((c.n * c.P * c.g.K + 255) / 256), dim3(256), 0, s, c, dst, iv);
 }
 
-void launch_ba_keyframe(const BatchCtx& c, const BaArgs& a, bool evict, hipStream_t s) {
-    const int K = c.g.K;
-    if (evict) {   // the insertion itself is the first launch of the solve (k_ba_insert_gate)
-        const int nb = (a.n_order * K + 255) / 256;
-        hipLaunchKernelGGL(k_ba_evict_min, dim3(nb), dim3(256), 0, s, c, a);
-        hipLaunchKernelGGL(k_ba_evict_move, dim3(nb), dim3(256), 0, s, c, a);
+// ---------------------------------------------------------------------------------------------
+// the keyframe chain: its steps written once over an issuer, which knows how the context and the
+// arguments reach a kernel — by value (direct launches) or through the device record (graph replays)
+// — and, the only other differences, how k_ba_schur receives `fused` and whether it is timed
+// ---------------------------------------------------------------------------------------------
+namespace {
+struct BaKernel { void (*val)(BatchCtx, BaArgs); void (*rec)(BaCtxRef, BaArgsRef); };
+#define BA_K(NAME) BaKernel{NAME, NAME##_rec}
+
+struct BaByValue {
+    const BatchCtx& c;
+    const BaArgs &a, &ev;   // the solve's arguments, the eviction's (remaining slots)
+    BaTiming* timing;       // when non-null: an event pair around every k_ba_schur launch
+    hipStream_t s;
+    void launch(BaKernel k, dim3 grid, dim3 block, bool evict = false) const {
+        hipLaunchKernelGGL(k.val, grid, block, 0, s, c, evict ? ev : a);
     }
+    void schur(dim3 grid, dim3 block, int fused) const {
+        BaArgs ai = a;
+        ai.fused_backsub = fused;
+        const bool rec = timing && timing->used < timing->cap;
+        if (rec) (void)hipEventRecord(timing->ev[2 * timing->used], s);
+        hipLaunchKernelGGL(k_ba_schur, grid, block, 0, s, c, ai);
+        if (rec) (void)hipEventRecord(timing->ev[2 * timing->used++ + 1], s);
+    }
+};
+
+struct BaByRecord {
+    const BatchCtx& c;      // the host copy of the record: grid sizes
+    const BaArgs &a, &ev;
+    BaCtxRef dc;            // into the device record the kernels read
+    BaArgsRef da, dev;
+    hipStream_t s;
+    void launch(BaKernel k, dim3 grid, dim3 block, bool evict = false) const {
+        hipLaunchKernelGGL(k.rec, grid, block, 0, s, dc, evict ? dev : da);
+    }
+    void schur(dim3 grid, dim3 block, int fused) const {
+        hipLaunchKernelGGL(k_ba_schur_rec, grid, block, 0, s, dc, da, fused);
+    }
+};
+
+// Eviction of the keyframe's slot (the insertion itself is the first launch of the solve).
+template <class Q> void ba_evict(const Q& q) {
+    const dim3 grid((q.ev.n_order * q.c.g.K + 255) / 256);
+    q.launch(BA_K(k_ba_evict_min), grid, dim3(256), true);
+    q.launch(BA_K(k_ba_evict_move), grid, dim3(256), true);
 }
 
-void launch_ba_schur(const BatchCtx& c, const BaArgs& a, hipStream_t s) {
-    BaArgs ai = a;
-    ai.fused_backsub = 0;   // a replay must not move the landmarks
-    hipLaunchKernelGGL(k_ba_schur, dim3(a.nsplit), dim3(BA_SCHUR_THREADS), 0, s, c, ai);
+// A solve's observation set of pair a.pair (gate, compaction, slot table): grids sized for the
+// window's maximum (counts live on the device; threads past them exit).
+template <class Q> void ba_prepare(const Q& q) {
+    const int K = q.c.g.K, n = q.a.n_order;
+    q.launch(BA_K(k_ba_insert_gate), dim3((n * K + 255) / 256), dim3(256));
+    const dim3 tiles((q.a.W * K + BA_TILE - 1) / BA_TILE + n * ((K + BA_TILE - 1) / BA_TILE));
+    q.launch(BA_K(k_ba_tilecount), tiles, dim3(256));
+    q.launch(BA_K(k_ba_tilescatter), tiles, dim3(256));
 }
 
-// A solve's observation set of pair a.pair (gate, compaction, slot table).
-static void launch_ba_prepare(const BatchCtx& c, const BaArgs& a, hipStream_t s) {
-    // grids sized for the window's maximum (counts live on the device; threads past them exit)
-    const int WK = a.W * c.g.K;
-    hipLaunchKernelGGL(k_ba_insert_gate, dim3((a.n_order * c.g.K + 255) / 256), dim3(256), 0, s, c, a);
-    const int ntiles = (WK + BA_TILE - 1) / BA_TILE + a.n_order * ((c.g.K + BA_TILE - 1) / BA_TILE);
-    hipLaunchKernelGGL(k_ba_tilecount, dim3(ntiles), dim3(256), 0, s, c, a);
-    hipLaunchKernelGGL(k_ba_tilescatter, dim3(ntiles), dim3(256), 0, s, c, a);
+template <class Q> void ba_schur(const Q& q, int fused) {
+    q.schur(dim3(q.a.nsplit), dim3(BA_SCHUR_THREADS), fused);
 }
+
+// the reduction to C, U_c, g_c (k_ba_reduce, k_ba_reduce_solve*): its blocks; its and the solve's threads
+dim3 ba_reduce_grid(const BaArgs& a) { return dim3(64 + (a.n_order * 27 + 63) / 64); }
+dim3 ba_solve_threads() { return dim3(64 * BA_SOLVE_WAVES); }
 
 // One linearisation of pair a.pair: the Schur pass (+ iteration it - 1's landmark update when
-// `it` > 0) and the reduction to C, U_c, g_c.
-static void launch_ba_linearize(const BatchCtx& c, const BaArgs& a, int it, hipStream_t s, BaTiming* timing,
-                                bool reduce = true) {
-    BaArgs ai = a;
-    const bool rec = timing && timing->used < timing->cap;
-    ai.fused_backsub = it > 0;   // iteration it - 1's landmark update happens inside this Schur pass
-    if (rec) (void)hipEventRecord(timing->ev[2 * timing->used], s);
-    hipLaunchKernelGGL(k_ba_schur, dim3(a.nsplit), dim3(BA_SCHUR_THREADS), 0, s, c, ai);
-    if (rec) (void)hipEventRecord(timing->ev[2 * timing->used++ + 1], s);
-    if (!reduce) return;   // k_ba_reduce_solve follows
-    hipLaunchKernelGGL(k_ba_reduce, dim3(64 + (a.n_order * 27 + 63) / 64), dim3(64 * BA_SOLVE_WAVES), 0, s, c, a);
+// `it` > 0) and, with `reduce`, the reduction to C, U_c, g_c (without: k_ba_reduce_solve follows).
+template <class Q> void ba_linearize(const Q& q, int it, bool reduce) {
+    ba_schur(q, it > 0 ? 1 : 0);
+    if (reduce) q.launch(BA_K(k_ba_reduce), ba_reduce_grid(q.a), ba_solve_threads());
 }
 
-static void launch_ba_backsub(const BatchCtx& c, const BaArgs& a, hipStream_t s) {
-    const int nb = (a.W * c.g.K + 255) / 256;
-    hipLaunchKernelGGL(k_ba_backsub, dim3(16 * nb), dim3(256), 0, s, c, a);   // the last iteration's
+// The camera solve of a.pair: after a reduction of its own (`split`: the kernel boundary instead
+// of the in-launch hand-off, tslam_ba_split_solve; a rig's body system), or reduce-and-solve.
+template <class Q> void ba_camera_solve(const Q& q, bool split, bool inertial) {
+    if (split)
+        q.launch(inertial ? BA_K(k_ba_solve_ine) : BA_K(k_ba_solve), dim3(1), ba_solve_threads());
+    else
+        q.launch(inertial ? BA_K(k_ba_reduce_solve_ine) : BA_K(k_ba_reduce_solve), ba_reduce_grid(q.a), ba_solve_threads());
+}
+
+template <class Q> void ba_backsub(const Q& q) {   // the last iteration's landmark update
+    q.launch(BA_K(k_ba_backsub), dim3(16 * ((q.a.W * q.c.g.K + 255) / 256)), dim3(256));
+}
+
+// A pair window's keyframe: eviction (when `evict`), gate / tile count / scatter, a.iters x
+// (Schur, then reduce-and-solve, or reduce + solve when `split`), back substitution.
+template <class Q> void ba_chain(const Q& q, bool evict, bool split, bool inertial) {
+    if (evict) ba_evict(q);
+    ba_prepare(q);
+    for (int it = 0; it < q.a.iters; ++it) {
+        ba_linearize(q, it, split);
+        ba_camera_solve(q, split, inertial);
+    }
+    ba_backsub(q);
+}
+}  // namespace
+
+void launch_ba_keyframe(const BatchCtx& c, const BaArgs& a, bool evict, hipStream_t s) {
+    if (evict) ba_evict(BaByValue{c, a, a, nullptr, s});
 }
 
 void launch_ba_solve(const BatchCtx& c, const BaArgs& a, hipStream_t s, BaTiming* timing, bool split, bool inertial) {
-    launch_ba_prepare(c, a, s);
-    const dim3 grid(64 + (a.n_order * 27 + 63) / 64), block(64 * BA_SOLVE_WAVES);
-    for (int it = 0; it < a.iters; ++it) {
-        launch_ba_linearize(c, a, it, s, timing, split);
-        if (split)   // the kernel boundary instead of the in-launch hand-off (tslam_ba_split_solve)
-            hipLaunchKernelGGL(inertial ? k_ba_solve_ine : k_ba_solve, dim3(1), block, 0, s, c, a);
-        else
-            hipLaunchKernelGGL(inertial ? k_ba_reduce_solve_ine : k_ba_reduce_solve, grid, block, 0, s, c, a);
-    }
-    launch_ba_backsub(c, a, s);
+    ba_chain(BaByValue{c, a, a, timing, s}, false, split, inertial);
+}
+
+void launch_ba_chain_rec(const BaRec& r, const BaRec* d, bool evict, bool split, bool inertial, hipStream_t s) {
+    const BaByRecord q{r.c, r.a, r.evict, (BaCtxRef)&d->c, (BaArgsRef)&d->a, (BaArgsRef)&d->evict, s};
+    ba_chain(q, evict, split, inertial);
+}
+
+void launch_ba_schur(const BatchCtx& c, const BaArgs& a, hipStream_t s) {
+    ba_schur(BaByValue{c, a, a, nullptr, s}, 0);   // a replay must not move the landmarks
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1690,35 +1723,6 @@ hipError_t ba_graph_set_record(hipGraphExec_t exec, hipGraphNode_t node, const B
     p.kernelParams = args;
     p.extra = nullptr;
     return hipGraphExecKernelNodeSetParams(exec, node, &p);
-}
-
-void launch_ba_chain_rec(const BaRec& r, const BaRec* d, bool evict, bool split, bool inertial, hipStream_t s) {
-    const BaCtxRef c = (BaCtxRef)&d->c;
-    const BaArgsRef a = (BaArgsRef)&d->a;
-    const BaArgsRef ev = (BaArgsRef)&d->evict;
-    const int K = r.c.g.K;
-    if (evict) {
-        const int nb = (r.evict.n_order * K + 255) / 256;
-        hipLaunchKernelGGL(k_ba_evict_min_rec, dim3(nb), dim3(256), 0, s, c, ev);
-        hipLaunchKernelGGL(k_ba_evict_move_rec, dim3(nb), dim3(256), 0, s, c, ev);
-    }
-    const BaArgs& ha = r.a;
-    const int WK = ha.W * K;
-    hipLaunchKernelGGL(k_ba_insert_gate_rec, dim3((ha.n_order * K + 255) / 256), dim3(256), 0, s, c, a);
-    const int ntiles = (WK + BA_TILE - 1) / BA_TILE + ha.n_order * ((K + BA_TILE - 1) / BA_TILE);
-    hipLaunchKernelGGL(k_ba_tilecount_rec, dim3(ntiles), dim3(256), 0, s, c, a);
-    hipLaunchKernelGGL(k_ba_tilescatter_rec, dim3(ntiles), dim3(256), 0, s, c, a);
-    const dim3 grid(64 + (ha.n_order * 27 + 63) / 64), block(64 * BA_SOLVE_WAVES);
-    for (int it = 0; it < ha.iters; ++it) {
-        hipLaunchKernelGGL(k_ba_schur_rec, dim3(ha.nsplit), dim3(BA_SCHUR_THREADS), 0, s, c, a, it > 0 ? 1 : 0);
-        if (split) {
-            hipLaunchKernelGGL(k_ba_reduce_rec, grid, block, 0, s, c, a);
-            hipLaunchKernelGGL(inertial ? k_ba_solve_ine_rec : k_ba_solve_rec, dim3(1), block, 0, s, c, a);
-        } else {
-            hipLaunchKernelGGL(inertial ? k_ba_reduce_solve_ine_rec : k_ba_reduce_solve_rec, grid, block, 0, s, c, a);
-        }
-    }
-    hipLaunchKernelGGL(k_ba_backsub_rec, dim3(16 * ((WK + 255) / 256)), dim3(256), 0, s, c, a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1874,21 +1878,22 @@ void launch_ba_rig_keyframe(const BatchCtx& c, const BaArgs& a, hipStream_t s) {
 void launch_ba_rig_solve(const BatchCtx& c, const BaArgs& a, hipStream_t s, BaTiming* timing, bool inertial) {
     BaArgs ap = a, ab = a;
     ab.pair = c.P;
+    const BaByValue qp{c, ap, ap, timing, s}, qb{c, ab, ab, nullptr, s};   // qp: pair ap.pair, set per step
     for (int p = 0; p < c.P; ++p) {
         ap.pair = p;
-        launch_ba_prepare(c, ap, s);
+        ba_prepare(qp);
     }
     for (int it = 0; it < a.iters; ++it) {
         for (int p = 0; p < c.P; ++p) {
             ap.pair = p;
-            launch_ba_linearize(c, ap, it, s, timing);
+            ba_linearize(qp, it, true);
         }
         hipLaunchKernelGGL(k_ba_rig_combine, dim3(64), dim3(64), 0, s, c, ab);
-        hipLaunchKernelGGL(inertial ? k_ba_solve_ine : k_ba_solve, dim3(1), dim3(64 * BA_SOLVE_WAVES), 0, s, c, ab);
+        ba_camera_solve(qb, true, inertial);
         hipLaunchKernelGGL(k_ba_rig_expand, dim3(c.P), dim3(64), 0, s, c, ab);
     }
     for (int p = 0; p < c.P; ++p) {
         ap.pair = p;
-        launch_ba_backsub(c, ap, s);
+        ba_backsub(qp);
     }
 }

@@ -154,16 +154,41 @@ static void ba_graphs_destroy(tslam_handle* h) {
     h->ba_cap_stream = nullptr;
 }
 
+// Keyframe g's factors of window `pair` — IMU rotation, inertial + initial velocity — popped out of
+// ba_imu / ba_ine into the insertion's arguments; zeros where none was given, and for a rig's pairs
+// (`use` false: a rig's inertial factor acts on its body window).  Marks the slot's inertial flag.
+static void ba_take_factors(tslam_handle* h, int pair, int64_t g, bool use, BaArgs& a) {
+    auto it = h->ba_imu.find({pair, g});
+    const bool rot = use && it != h->ba_imu.end();
+    for (int e = 0; e < 10; ++e) a.imu[e] = rot ? it->second[e] : 0.0;
+    if (it != h->ba_imu.end()) h->ba_imu.erase(it);
+    auto jt = h->ba_ine.find({pair, g});
+    const bool has = use && jt != h->ba_ine.end();
+    for (int e = 0; e < TS_BA_INE; ++e) a.ine[e] = has ? jt->second[e] : 0.0;
+    for (int e = 0; e < 3; ++e) a.vel0[e] = has ? jt->second[TS_BA_INE + e] : 0.0;
+    if (jt != h->ba_ine.end()) h->ba_ine.erase(jt);
+    h->ba_ine_slot[pair][a.slot] = has && a.ine[28] > 0.0;
+}
+
+// The inertial kernels when a factor links two keyframes of the window (the oldest's points out of it).
+static bool ba_window_inertial(const tslam_handle* h, int pair, const BaArgs& a) {
+    bool ine = false;
+    for (int k = 1; k < a.n_order; ++k) ine = ine || h->ba_ine_slot[pair][a.order[k]];
+    return ine;
+}
+
 // A8: every keyframe of the current batch (g % ba_kf_interval == 0) enters each pair's window,
-// evicting the oldest when the window is full, and the window is solved (per pair, or for a rig
-// one joint body solve: launch_ba_rig_solve).  Host bookkeeping of the slots only; nothing
-// synchronises.  `fe_body`: the rig front end's snapshot of the batch (rig-level A8).
+// evicting the oldest when the window is full, and the window is solved: per pair one keyframe chain
+// (eviction + solve, issued directly or replayed from a graph), or for a rig every pair's eviction and
+// one joint body solve.  Host bookkeeping of the slots only; nothing synchronises.  `fe_body`: the rig
+// front end's snapshot of the batch (rig-level A8).
 static hipError_t run_ba(tslam_handle* h, const BatchCtx& c, hipStream_t s, const double* fe, const double* fe_body,
                          const int32_t* kf_assoc) {
     const int W = h->prm.ba_window, iv = h->prm.ba_kf_interval;
+    const bool rig = ba_rig(h);
     // pair windows replay their keyframe chains from graphs (not while Schur launches are timed)
-    const bool graph = h->ba_graph && !ba_rig(h) && !h->ba_timing.ev;
-    std::vector<BaArgs> ev_args;
+    const bool graph = h->ba_graph && !rig && !h->ba_timing.ev;
+    BaTiming* timing = h->ba_timing.ev ? &h->ba_timing : nullptr;
     for (int64_t g = c.g0; g < c.g0 + c.n; ++g) {
         if (g % iv != 0 || g <= h->ba_last) continue;
         BaArgs a = ba_args(h);
@@ -175,82 +200,44 @@ static hipError_t run_ba(tslam_handle* h, const BatchCtx& c, hipStream_t s, cons
         const int nocc = ba_order(h, -1, ord);
         a.prev = nocc ? ord[nocc - 1] : -1;
         const bool evict = h->ba_frame[a.slot] >= 0;
-        if (evict) a.n_order = ba_order(h, a.slot, a.order);
-        const bool rig = ba_rig(h);
         if (rig) {   // the body pose first, every pair's camera E_p^-1 B (and the body's inertial factor)
             a.fe_body = fe_body;
             a.pose_given = 1;
-            auto jt = h->ba_ine.find({h->P, g});
-            const bool has = jt != h->ba_ine.end();
-            for (int e = 0; e < TS_BA_INE; ++e) a.ine[e] = has ? jt->second[e] : 0.0;
-            for (int e = 0; e < 3; ++e) a.vel0[e] = has ? jt->second[TS_BA_INE + e] : 0.0;
-            if (has) h->ba_ine.erase(jt);
-            h->ba_ine_slot[h->P][a.slot] = has && a.ine[28] > 0.0;
+            ba_take_factors(h, h->P, g, true, a);
             launch_ba_rig_keyframe(c, a, s);
         }
-        // per pair: the keyframe's IMU rotation factor, inertial factor and initial velocity (zero
-        // for a rig's pairs), inserted by the solve's first launch (k_ba_insert_gate)
-        std::vector<std::array<double, 10 + TS_BA_INE + 3>> kfi((size_t)h->P);
+        // the keyframe's record: the eviction's arguments (the remaining slots) from before the slot
+        // bookkeeping moves, the solve's from after it
+        BaRec r{c, a, a};
+        if (evict) r.evict.n_order = ba_order(h, a.slot, r.evict.order);
+        h->ba_frame[a.slot] = g;
+        h->ba_nkf += 1;
+        h->ba_last = g;
+        r.a.n_order = ba_order(h, -1, r.a.order);
+        h->ba_solved.resize(h->P);
         for (int p = 0; p < h->P; ++p) {
-            a.pair = p;
-            auto& v = kfi[(size_t)p];
-            auto it = h->ba_imu.find({p, g});   // the keyframe's IMU rotation factor (if given)
-            for (int e = 0; e < 10; ++e) v[e] = (!rig && it != h->ba_imu.end()) ? it->second[e] : 0.0;
-            if (it != h->ba_imu.end()) h->ba_imu.erase(it);
-            auto jt = h->ba_ine.find({p, g});   // and its inertial factor + initial velocity
-            const bool has = !rig && jt != h->ba_ine.end();
-            for (int e = 0; e < TS_BA_INE + 3; ++e) v[10 + e] = has ? jt->second[e] : 0.0;
-            if (jt != h->ba_ine.end()) h->ba_ine.erase(jt);
-            h->ba_ine_slot[p][a.slot] = has && v[10 + 28] > 0.0;
-            if (graph)
-                ev_args.push_back(a);   // the eviction runs first in the pair's chain below
-            else
-                launch_ba_keyframe(c, a, evict, s);   // eviction only
+            r.evict.pair = r.a.pair = p;
+            ba_take_factors(h, p, g, !rig, r.a);   // inserted by the solve's first launch (k_ba_insert_gate)
+            if (!graph) launch_ba_keyframe(c, r.evict, evict, s);   // the eviction, by value
+            if (rig) continue;   // every pair's eviction ahead of the joint solve
+            for (int e = 0; e < 12; ++e) r.a.icfg[e] = h->ba_icfg[p][e];
+            const bool ine = ba_window_inertial(h, p, r.a);
+            if (!graph) launch_ba_solve(c, r.a, s, timing, h->ba_split, ine);
+            else if (const hipError_t e = ba_chain_graph(h, r, evict, h->ba_split, ine, s); e != hipSuccess) return e;
+            h->ba_solved[p] = r.a;
         }
-        for (int e = 0; e < 10; ++e) a.imu[e] = 0.0;
-        for (int e = 0; e < TS_BA_INE; ++e) a.ine[e] = 0.0;
-        for (int e = 0; e < 3; ++e) a.vel0[e] = 0.0;
         for (auto it = h->ba_imu.begin(); it != h->ba_imu.end();)   // factors of frames already past
             it = it->first.second < g ? h->ba_imu.erase(it) : std::next(it);
         for (auto it = h->ba_ine.begin(); it != h->ba_ine.end();)
             it = it->first.second < g ? h->ba_ine.erase(it) : std::next(it);
-        h->ba_frame[a.slot] = g;
-        h->ba_nkf += 1;
-        h->ba_last = g;
-        a.n_order = ba_order(h, -1, a.order);
-        h->ba_solved.resize(h->P);
         if (rig) {
-            for (int e = 0; e < 12; ++e) a.icfg[e] = h->ba_icfg[h->P][e];
-            bool ine = false;
-            for (int k = 1; k < a.n_order; ++k) ine = ine || h->ba_ine_slot[h->P][a.order[k]];
-            launch_ba_rig_solve(c, a, s, h->ba_timing.ev ? &h->ba_timing : nullptr, ine);
+            for (int e = 0; e < 12; ++e) r.a.icfg[e] = h->ba_icfg[h->P][e];
+            launch_ba_rig_solve(c, r.a, s, timing, ba_window_inertial(h, h->P, r.a));
             for (int p = 0; p < h->P; ++p) {
-                h->ba_solved[p] = a;
+                h->ba_solved[p] = r.a;
                 h->ba_solved[p].pair = p;
             }
-            continue;
         }
-        for (int p = 0; p < h->P; ++p) {
-            a.pair = p;
-            const auto& v = kfi[(size_t)p];
-            for (int e = 0; e < 10; ++e) a.imu[e] = v[e];
-            for (int e = 0; e < TS_BA_INE; ++e) a.ine[e] = v[10 + e];
-            for (int e = 0; e < 3; ++e) a.vel0[e] = v[10 + TS_BA_INE + e];
-            for (int e = 0; e < 12; ++e) a.icfg[e] = h->ba_icfg[p][e];
-            // the inertial kernels when a factor links two keyframes of the window (the oldest
-            // keyframe's factor points out of it)
-            bool ine = false;
-            for (int k = 1; k < a.n_order; ++k) ine = ine || h->ba_ine_slot[p][a.order[k]];
-            if (graph) {
-                const BaRec r{c, ev_args[(size_t)p], a};
-                const hipError_t e = ba_chain_graph(h, r, evict, h->ba_split, ine, s);
-                if (e != hipSuccess) return e;
-            } else {
-                launch_ba_solve(c, a, s, h->ba_timing.ev ? &h->ba_timing : nullptr, h->ba_split, ine);
-            }
-            h->ba_solved[p] = a;
-        }
-        if (graph) ev_args.clear();
     }
     return hipSuccess;
 }

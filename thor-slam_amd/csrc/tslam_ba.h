@@ -172,6 +172,8 @@ __device__ __forceinline__ BaPair ba_pair(const BatchCtx& c, const BaArgs& a, in
 void launch_ba_snapshot(const BatchCtx& c, double* dst, hipStream_t s);
 // the batch's keyframes' temporal-match chains back to the previous keyframe frame (interval iv)
 void launch_ba_kf_assoc(const BatchCtx& c, int32_t* dst, int iv, hipStream_t s);
+// a pair window's keyframe chain (k_ba.hip ba_chain) by value: its eviction here (a.order = the
+// remaining slots), the rest in launch_ba_solve
 void launch_ba_keyframe(const BatchCtx& c, const BaArgs& a, bool evict, hipStream_t s);
 // timing: when non-null, an event pair is recorded around every k_ba_schur launch (profiling)
 struct BaTiming {
@@ -199,9 +201,7 @@ struct BaRec {
     BaArgs evict;
     BaArgs a;
 };
-// The keyframe's chain on the record d (grids from the host copy `r`): eviction (when `evict`),
-// gate / tile count / scatter, a.iters x (Schur + reduce-and-solve, or reduce + solve when
-// `split`), back substitution — the launches of launch_ba_keyframe + launch_ba_solve, by pointer.
+// the chain on the record d (grids from the host copy r): launch_ba_keyframe + launch_ba_solve, by pointer
 void launch_ba_chain_rec(const BaRec& r, const BaRec* d, bool evict, bool split, bool inertial, hipStream_t s);
 // k_ba_setrec: copies the record (by value) to d
 void launch_ba_setrec(const BaRec& r, BaRec* d, hipStream_t s);
