@@ -1025,6 +1025,88 @@ int tslam_tsdf_align_buffers(tslam_handle* h, void** world_T_cam, void** stats);
 int tslam_tsdf_integrate_aligned(tslam_handle* h, const void* color, const void* depth, int64_t stride_bytes, int n_frames,
                                  void* stream);
 
+/* Depth registration: the depth of a pair's rectified left camera forward-warped into a colour
+ * camera with a z-buffer, so that a stereo rig with a centre colour camera gets a coloured dense map
+ * and depth aligned to that camera (added within ABI 21: eight new symbols and two structs; nothing
+ * else changes, and a handle that calls none of them behaves as before).  Spec:
+ * thor_slam_amd/depth_register.py.  Every valid depth pixel (0 < D <= max_depth_mm) is projected
+ * into the undistorted colour camera and covers the colour pixels of its footprint (at most
+ * max_splat per axis, always its nearest pixel); per colour pixel the nearest depth wins.  Outputs
+ * per slot: the registered depth u16 mm [color_height][color_width] in the undistorted colour camera
+ * (0 where nothing landed); bgr u8 [height][width][3], the raw colour pixel (through the table) that
+ * sees each depth pixel; mask u8 [height][width], 1 where the colour camera sees the depth pixel (its
+ * depth there is within tol_mm of the nearest), else 0 with bgr 0.  Stereo handles only; one state
+ * per pair.
+ *
+ * tslam_depth_register_init: the parameters of pair `pair` (its rectified left camera is the depth
+ *   camera) and output slots for max_frames frames (1..65535).  The depth image is width x height
+ *   (16 .. the handle's size each, dense rows, as tslam_stereo_depth_images allows); the colour
+ *   image color_width x color_height (1..16384 each) with the undistorted pinhole f_c, cxc, cyc and
+ *   the host table `map` i32 [color_height][color_width][2] (undistorted pixel -> raw pixel times 32,
+ *   what tslam_rgbd_undistort writes; copied to the device) or NULL (identity); color_T_rect 12
+ *   doubles, 3 x 4 row-major [R | t]; max_depth_mm 1..65535; tol_mm 0..65535; max_splat 1..8;
+ *   reserved 0.  TSLAM_EINVAL otherwise; TSLAM_ESTATE on an RGB-D handle or inside a batch.  May be
+ *   called again (outside a batch); the buffers are resized, so a re-init that fails to allocate
+ *   (TSLAM_ENOMEM) leaves the pair without a state.  tslam_reset keeps parameters and buffers;
+ *   tslam_destroy frees them.
+ * tslam_depth_register: n_frames (0..max_frames) frames of caller-supplied device planes (depth u16
+ *   mm, frames depth_stride bytes apart, even; raw BGR colour, frames color_stride bytes apart) into
+ *   slots first_slot .. first_slot + n_frames - 1, every other slot keeping its contents; the stereo
+ *   matcher's slots (tslam_stereo_depth_buffers) are one such caller.  Three launches on `stream`
+ *   (NULL: the handle's last stream), nothing waits.  TSLAM_ESTATE without the pair's state or
+ *   inside a batch; TSLAM_EINVAL for a null plane, n_frames or slots out of range, or a stride below
+ *   one image while n_frames > 1.
+ * tslam_depth_register_blank: slots first_slot .. first_slot + n_frames - 1 of bgr and mask set to
+ *   zero on `stream`: a frame that came without a colour image.  The registered depth of those slots
+ *   keeps its contents.  Refusals as tslam_depth_register's for the state, the batch and the slots.
+ * tslam_depth_register_buffers: the device pointers and, in slot_bytes[3], the bytes of one slot of
+ *   the registered depth, bgr and mask.  Every output argument may be NULL.
+ * tslam_depth_register_read: one slot copied out (synchronises); NULL pointers are skipped.
+ * tslam_depth_register_profile: enable != 0 records events around the three passes (clear, splat,
+ *   gather) of every later tslam_depth_register call; with pass_ms non-NULL the newest timed call's
+ *   three times in milliseconds are read first (waits for that call; TSLAM_ESTATE when there is none).
+ * tslam_tsdf_integrate_rect_color: tslam_tsdf_integrate_rect with colour that has a stride of its
+ *   own and a visibility mask: `color` BGR u8 [H][W][3] per frame (color_stride apart), `mask` u8
+ *   [H][W] per frame (mask_stride apart) or NULL.  A voxel's colour is updated only where the sampled
+ *   pixel's mask is non-zero; NULL means every pixel, which is tslam_tsdf_integrate_rgbd's colour
+ *   integration exactly.  tsdf and weight are those of tslam_tsdf_integrate_rect bit for bit.
+ *   TSLAM_EINVAL for null colour or a colour / mask stride below one image (for any n_frames: these
+ *   strides are never taken from the depth's);
+ *   TSLAM_ESTATE without the colour layer; then the refusals of tslam_tsdf_integrate_rect.
+ * tslam_tsdf_integrate_rig_color: tslam_tsdf_integrate_rig with one colour descriptor per camera in
+ *   the parallel array `colors` (cams[].color must be NULL): all cameras coloured or none, as there;
+ *   a camera without a colour image passes any image and a zero mask.  TSLAM_EINVAL, beside
+ *   tslam_tsdf_integrate_rig's, for a non-NULL cams[].color, descriptors mixed coloured and not, or a
+ *   colour / mask stride below one image.  A refused call changes nothing. */
+typedef struct {
+    int32_t width, height;              /* the depth image */
+    int32_t color_width, color_height;  /* the raw colour image */
+    double f_c, cxc, cyc;               /* the undistorted colour camera */
+    const int32_t* map;                 /* host table or NULL */
+    double color_T_rect[12];
+    int32_t max_depth_mm, tol_mm, max_splat;
+    int32_t reserved;                   /* 0 */
+} tslam_depth_register_params;
+typedef struct {
+    const void* color;     /* device BGR u8 [n_frames][H][W][3], frame f at color + f * color_stride; NULL: no colour */
+    int64_t color_stride;
+    const void* mask;      /* device u8 [n_frames][H][W], frame f at mask + f * mask_stride; NULL: every pixel */
+    int64_t mask_stride;
+} tslam_tsdf_rig_color;
+int tslam_depth_register_init(tslam_handle* h, int pair, const tslam_depth_register_params* params, int max_frames);
+int tslam_depth_register(tslam_handle* h, int pair, const void* depth, int64_t depth_stride, const void* color,
+                         int64_t color_stride, int n_frames, int first_slot, void* stream);
+int tslam_depth_register_blank(tslam_handle* h, int pair, int n_frames, int first_slot, void* stream);
+int tslam_depth_register_buffers(tslam_handle* h, int pair, void** registered_depth, void** bgr, void** mask,
+                                 int64_t* slot_bytes);
+int tslam_depth_register_read(tslam_handle* h, int pair, int slot, uint16_t* registered_depth, uint8_t* bgr, uint8_t* mask);
+int tslam_depth_register_profile(tslam_handle* h, int enable, double* pass_ms);
+int tslam_tsdf_integrate_rect_color(tslam_handle* h, int pair, const void* color, int64_t color_stride, const void* mask,
+                                    int64_t mask_stride, const void* depth, int64_t stride_bytes, int n_frames,
+                                    int64_t first_frame, const double* world_T_cam, void* stream);
+int tslam_tsdf_integrate_rig_color(tslam_handle* h, const tslam_tsdf_rig_camera* cams, const tslam_tsdf_rig_color* colors,
+                                   int n_cams, int n_frames, int64_t first_frame, const double* world_T_base, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

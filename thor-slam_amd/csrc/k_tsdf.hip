@@ -15,7 +15,9 @@
 //                     each of those frames project the centre (f64), nearest depth pixel through
 //                     the undistortion table, truncated signed distance, weighted average;
 //                     with the colour layer, the same pixel's colour averaged into the voxels
-//                     inside the truncation band (nvblox's colour integration).
+//                     inside the truncation band (nvblox's colour integration), where the
+//                     pixel's visibility mask, if the call has one, is non-zero (colour registered
+//                     to the depth, k_depth_register.hip).
 //
 // A rig (tslam_tsdf_integrate_rig) integrates several cameras in the same launch:
 //   k_tsdf_rig_poses         per view v = f * n_cams + ci: world_T_cam = (E_0^-1 T_abs(f)) E_pair from
@@ -154,7 +156,7 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate(std::conditional_t<RIG, 
             m &= m - 1;
             double fx, fy, cx, cy;
             const int32_t* map;
-            const uint8_t *depth, *color;
+            const uint8_t *depth, *color, *mask;
             if constexpr (RIG) {   // f is a view: its frame's image of its camera
                 f = __builtin_amdgcn_readfirstlane(f);
                 const TsdfRigCam& cm = a.cams[f % a.n_cams];
@@ -162,12 +164,14 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate(std::conditional_t<RIG, 
                 fx = cm.fx, fy = cm.fy, cx = cm.cx, cy = cm.cy;
                 map = cm.map;
                 depth = cm.depth + fo;
-                color = cm.color + fo;
+                color = cm.color + (size_t)(f / a.n_cams) * cm.color_stride;
+                mask = cm.mask ? cm.mask + (size_t)(f / a.n_cams) * cm.mask_stride : nullptr;
             } else {
                 fx = a.fx, fy = a.fy, cx = a.cx, cy = a.cy;
                 map = a.map;
                 depth = a.depth + (size_t)f * a.stride;
-                color = a.color + (size_t)f * a.stride;
+                color = a.color + (size_t)f * a.color_stride;
+                mask = a.mask ? a.mask + (size_t)f * a.mask_stride : nullptr;
             }
             const double* q = s_p + f * TSDF_POSE;   // LDS broadcast
             const double pz = ((q[6] * X + q[7] * Y) + q[8] * Z) + q[11];
@@ -203,7 +207,8 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate(std::conditional_t<RIG, 
             const double w1 = w + 1.0;
             ts = (double)(float)((ts * w + obs) / w1);   // stored as f32 after every frame (as the oracle)
             w = (double)(float)fmin(w1, a.max_weight);
-            if (a.col && sdf <= a.trunc) {   // colour inside the truncation band: the same pixel's BGR
+            // colour inside the truncation band: the same pixel's BGR, where its mask (if any) is set
+            if (a.col && sdf <= a.trunc && (!mask || mask[(size_t)iy * a.W + ix])) {
                 const uint8_t* px = color + ((size_t)iy * a.W + ix) * 3;
                 const double c1 = cw + 1.0;
                 cr = (double)(float)((cr * cw + (double)px[2]) / c1);
@@ -363,6 +368,10 @@ static void tsdf_integrate_posed(const Args& a, double* poses, hipStream_t s, co
     }
     Args b = a;
     b.poses = poses;
+    if (!b.color_stride) b.color_stride = b.stride;   // colour in the depth's records
+    if constexpr (std::is_same_v<Args, TsdfRigArgs>)
+        for (int ci = 0; ci < b.n_cams; ++ci)
+            if (!b.cams[ci].color_stride) b.cams[ci].color_stride = b.cams[ci].stride;
     const int nbx = (a.nx + TSDF_BX - 1) / TSDF_BX, nby = (a.ny + TSDF_BY - 1) / TSDF_BY,
               nbz = (a.nz + TSDF_BZ - 1) / TSDF_BZ;
     constexpr bool RIG = std::is_same_v<Args, TsdfRigArgs>;

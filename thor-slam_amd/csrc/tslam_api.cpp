@@ -466,6 +466,7 @@ int tslam_destroy(tslam_handle* h) {
     for (hipStream_t st : {h->as_front, h->as_back, h->as_ba})
         if (st) (void)hipStreamDestroy(st);
     ba_destroy(h);   // its events, then the graph cache
+    register_destroy(h);
     free_all(h);
     delete h;
     return TSLAM_OK;

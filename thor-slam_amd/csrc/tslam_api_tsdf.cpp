@@ -199,9 +199,11 @@ int tslam_tsdf_init(tslam_handle* h, const double* origin, const int32_t* dims, 
     return TSLAM_OK;
 }
 
-// its own order of refusals: the depth and the stride before the batch
+// its own order of refusals: the depth and the stride before the batch.  color_stride 0: the colour
+// lies in the depth's records (stride_bytes apart); mask: TsdfArgs::mask, or null
 static int tsdf_integrate(tslam_handle* h, int pair, const void* color, const void* depth, int64_t stride_bytes,
-                          int n_frames, int64_t first_frame, const double* world_T_cam, void* stream, bool rect = false) {
+                          int n_frames, int64_t first_frame, const double* world_T_cam, void* stream, bool rect = false,
+                          int64_t color_stride = 0, const void* mask = nullptr, int64_t mask_stride = 0) {
     if (!h || pair < 0 || pair >= h->P) return fail(TSLAM_EINVAL, "bad handle or pair");
     BA_FLUSH(h);
     if (!h->tsdf_on) return no_volume();
@@ -214,11 +216,14 @@ static int tsdf_integrate(tslam_handle* h, int pair, const void* color, const vo
     const BatchCtx c = make_ctx(h);
     TsdfArgs a = integrate_args(h, pair_camera(h, pair, rect), color != nullptr);
     a.stride = stride_bytes;
+    a.color_stride = color_stride ? color_stride : stride_bytes;
+    a.mask_stride = mask_stride;
     const TsdfFollowCall fc = follow_call(h);
     for (int b0 = 0; b0 < n_frames; b0 += TSDF_MAX_FRAMES) {
         a.n = std::min(TSDF_MAX_FRAMES, n_frames - b0);
         a.depth = static_cast<const uint8_t*>(depth) + (size_t)b0 * stride_bytes;
-        a.color = color ? static_cast<const uint8_t*>(color) + (size_t)b0 * stride_bytes : nullptr;
+        a.color = color ? static_cast<const uint8_t*>(color) + (size_t)b0 * a.color_stride : nullptr;
+        a.mask = mask ? static_cast<const uint8_t*>(mask) + (size_t)b0 * mask_stride : nullptr;
         const double* wtc;
         if (const int rc = stage_poses(world_T_cam ? world_T_cam + (size_t)16 * b0 : nullptr, a.n, h->d_tsdf_wTc, s, &wtc); rc != TSLAM_OK) return rc;
         launch_tsdf(c, pair, f0 + b0, wtc, a, h->d_tsdf_poses, s, h->tsdf_follow_on && b0 == 0 ? &fc : nullptr);
@@ -298,10 +303,24 @@ int tslam_tsdf_integrate_rect(tslam_handle* h, int pair, const void* depth, int6
     return tsdf_integrate(h, pair, nullptr, depth, stride_bytes, n_frames, first_frame, world_T_cam, stream, true);
 }
 
+int tslam_tsdf_integrate_rect_color(tslam_handle* h, int pair, const void* color, int64_t color_stride, const void* mask,
+                                    int64_t mask_stride, const void* depth, int64_t stride_bytes, int n_frames,
+                                    int64_t first_frame, const double* world_T_cam, void* stream) {
+    if (!h) return fail(TSLAM_EINVAL, "bad handle or pair");
+    if (!color) return fail(TSLAM_EINVAL, "null colour images");
+    if (!h->tsdf_color) return fail(TSLAM_ESTATE, "no colour layer (tslam_tsdf_color before tslam_tsdf_init)");
+    // strides of their own, so at least one image each, whatever n_frames is
+    if (color_stride < 3LL * h->W * h->H || (mask && mask_stride < (int64_t)h->W * h->H))
+        return fail(TSLAM_EINVAL, "bad colour / mask stride");
+    return tsdf_integrate(h, pair, color, depth, stride_bytes, n_frames, first_frame, world_T_cam, stream, true,
+                          color_stride, mask, mask_stride);
+}
+
 // Several cameras of a rig in one launch per chunk, on the body pose (k_tsdf.hip, launch_tsdf_rig).
-// Its own order of refusals: the rig before the volume.
-int tslam_tsdf_integrate_rig(tslam_handle* h, const tslam_tsdf_rig_camera* cams, int n_cams, int n_frames,
-                             int64_t first_frame, const double* world_T_base, void* stream) {
+// Its own order of refusals: the rig before the volume.  colors null: the colour of camera ci is
+// cams[ci].color, in its depth's records; else colors[ci], with strides of its own and a mask.
+static int tsdf_integrate_rig(tslam_handle* h, const tslam_tsdf_rig_camera* cams, const tslam_tsdf_rig_color* colors,
+                              int n_cams, int n_frames, int64_t first_frame, const double* world_T_base, void* stream) {
     if (!h || !cams) return fail(TSLAM_EINVAL, "bad argument");
     BA_FLUSH(h);
     if (!h->rig) return fail(TSLAM_ESTATE, "no rig set (tslam_set_rig)");
@@ -309,13 +328,20 @@ int tslam_tsdf_integrate_rig(tslam_handle* h, const tslam_tsdf_rig_camera* cams,
     if (h->in_batch) return fail(TSLAM_ESTATE, "tslam_tsdf_integrate_rig inside a batch");
     if (n_cams < 1 || n_cams > TS_RIG_MAXP) return fail(TSLAM_EINVAL, "n_cams must be 1..8");
     if (n_frames < 0) return fail(TSLAM_EINVAL, "n_frames must be >= 0");
-    const bool color = cams[0].color != nullptr;
+    const bool color = colors ? colors[0].color != nullptr : cams[0].color != nullptr;
     for (int ci = 0; ci < n_cams; ++ci) {
         const tslam_tsdf_rig_camera& cm = cams[ci];
+        if (colors) {
+            const tslam_tsdf_rig_color& cc = colors[ci];
+            if (cm.color) return fail(TSLAM_EINVAL, "colour comes from the colour descriptors: cams[].color must be NULL");
+            if ((cc.color != nullptr) != color) return fail(TSLAM_EINVAL, "colour for all cameras or for none");
+            if (cc.color && (cc.color_stride < 3LL * h->W * h->H || (cc.mask && cc.mask_stride < (int64_t)h->W * h->H)))
+                return fail(TSLAM_EINVAL, "bad colour / mask stride");
+        }
         if (cm.pair < 0 || cm.pair >= h->P || (ci > 0 && cm.pair <= cams[ci - 1].pair))
             return fail(TSLAM_EINVAL, "pairs must be strictly ascending and in range");
         if (!cm.depth || (n_frames > 1 && cm.stride_bytes < 2LL * h->W * h->H)) return fail(TSLAM_EINVAL, "bad depth / stride");
-        if ((cm.color != nullptr) != color) return fail(TSLAM_EINVAL, "colour for all cameras or for none");
+        if (!colors && (cm.color != nullptr) != color) return fail(TSLAM_EINVAL, "colour for all cameras or for none");
     }
     if (color && !h->tsdf_color) return fail(TSLAM_EINVAL, "colour without the colour layer (tslam_tsdf_color)");
     int f0;
@@ -338,6 +364,8 @@ int tslam_tsdf_integrate_rig(tslam_handle* h, const tslam_tsdf_rig_camera* cams,
         r.cy = k.cy;
         r.map = k.map;
         r.stride = cams[ci].stride_bytes;
+        r.color_stride = colors ? colors[ci].color_stride : r.stride;
+        r.mask_stride = colors ? colors[ci].mask_stride : 0;
     }
     // chunks of whole frames, so that every chunk's views fit the pose table and stay frame-major
     const int chunk = TSDF_MAX_FRAMES / n_cams;
@@ -347,7 +375,10 @@ int tslam_tsdf_integrate_rig(tslam_handle* h, const tslam_tsdf_rig_camera* cams,
         for (int ci = 0; ci < n_cams; ++ci) {
             const size_t o = (size_t)b0 * cams[ci].stride_bytes;
             a.cams[ci].depth = static_cast<const uint8_t*>(cams[ci].depth) + o;
-            a.cams[ci].color = color ? static_cast<const uint8_t*>(cams[ci].color) + o : nullptr;
+            const void* col = colors ? colors[ci].color : cams[ci].color;
+            const void* msk = colors ? colors[ci].mask : nullptr;
+            a.cams[ci].color = color ? static_cast<const uint8_t*>(col) + (size_t)b0 * a.cams[ci].color_stride : nullptr;
+            a.cams[ci].mask = color && msk ? static_cast<const uint8_t*>(msk) + (size_t)b0 * a.cams[ci].mask_stride : nullptr;
         }
         const double* wtb;
         if (const int rc = stage_poses(world_T_base ? world_T_base + (size_t)16 * b0 : nullptr, nf, h->d_tsdf_wTc, s, &wtb); rc != TSLAM_OK) return rc;
@@ -356,6 +387,17 @@ int tslam_tsdf_integrate_rig(tslam_handle* h, const tslam_tsdf_rig_camera* cams,
         if (world_T_base) HIPCHK(hipStreamSynchronize(s));   // the staged host poses are reused
     }
     return TSLAM_OK;
+}
+
+int tslam_tsdf_integrate_rig(tslam_handle* h, const tslam_tsdf_rig_camera* cams, int n_cams, int n_frames,
+                             int64_t first_frame, const double* world_T_base, void* stream) {
+    return tsdf_integrate_rig(h, cams, nullptr, n_cams, n_frames, first_frame, world_T_base, stream);
+}
+
+int tslam_tsdf_integrate_rig_color(tslam_handle* h, const tslam_tsdf_rig_camera* cams, const tslam_tsdf_rig_color* colors,
+                                   int n_cams, int n_frames, int64_t first_frame, const double* world_T_base, void* stream) {
+    if (!colors) return fail(TSLAM_EINVAL, "bad argument");
+    return tsdf_integrate_rig(h, cams, colors, n_cams, n_frames, first_frame, world_T_base, stream);
 }
 
 // -- the volume read and written on the host ------------------------------------------------------

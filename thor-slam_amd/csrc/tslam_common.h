@@ -303,11 +303,18 @@ struct TsdfArgs {
     double fx, fy, cx, cy;
     const int32_t* map;        // [H][W][2] undistortion table (fixed point, 5 bits) or null
     const double* poses;       // [n][TSDF_POSE]
-    // colour layer (null when off): frame 0's BGR image (frames `stride` bytes apart, as the
-    // depth), the running colour [nv][3] (R, G, B) f32 and its weight f32
+    // colour layer (null when off): frame 0's BGR image (frames `color_stride` bytes apart, below),
+    // the running colour [nv][3] (R, G, B) f32 and its weight f32
     const uint8_t* color;
     float* col;
     float* col_w;
+    // colour with a stride of its own and a visibility mask (tslam_tsdf_integrate_rect_color: colour
+    // registered to the depth, thor_slam_amd/depth_register.py): color_stride 0 = `stride`; mask u8
+    // [H][W] per frame, mask_stride bytes apart: a voxel's colour is updated only where the sampled
+    // pixel's mask is non-zero; null = every pixel
+    int64_t color_stride;
+    const uint8_t* mask;
+    int64_t mask_stride;
     // the rolling window's record (null: the volume's corner is ox, oy, oz as they stand; else the
     // corner is o + s * (double)win->shift[a], thor_slam_amd/dense_follow.py)
     const struct TsdfWindow* win;
@@ -352,10 +359,13 @@ void launch_tsdf(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev
 #define TS_RIG_MAXP 8   // pairs of a rig (tslam_create: n_pairs <= 8)
 struct TsdfRigCam {
     const uint8_t* depth;      // this camera's frame 0 (u16 mm), frames `stride` bytes apart
-    const uint8_t* color;      // BGR u8 with the same stride (null: TsdfArgs::col is null too)
+    const uint8_t* color;      // BGR u8, frames `color_stride` apart (null: TsdfArgs::col is null too)
     const int32_t* map;        // the raw camera's undistortion table, or null (rectified depth)
     int64_t stride;
     double fx, fy, cx, cy;
+    int64_t color_stride;      // 0 = `stride`
+    const uint8_t* mask;       // as TsdfArgs::mask, or null
+    int64_t mask_stride;
 };
 struct TsdfRigArgs : TsdfArgs {
     int n_cams;
@@ -470,6 +480,26 @@ struct StereoFilterArgs {
 hipError_t launch_sd_filter(const StereoFilterArgs& a, hipStream_t s);
 // n values of a caller's disp32 plane into dst, clamped to 8191
 hipError_t launch_sd_filter_load(const uint16_t* src, uint16_t* dst, size_t n, hipStream_t s);
+// depth registration (k_depth_register.hip; thor_slam_amd/depth_register.py): n frames of depth of a
+// W x H pinhole camera forward-warped into a Wc x Hc colour camera through a z-buffer
+struct DepthRegArgs {
+    int W, H, Wc, Hc, n;
+    double fx, fy, cx, cy;     // the depth camera
+    double fc, cxc, cyc;       // the undistorted colour camera
+    double T[12];              // color_T_rect, 3 x 4 row-major
+    int max_depth_mm, tol_mm, max_splat;
+    const int32_t* map;        // [Hc][Wc][2] undistorted -> raw colour pixel (fixed point, 5 bits) or null
+    const uint8_t* depth;      // frame 0's depth (u16 mm, dense rows), frames depth_stride bytes apart
+    int64_t depth_stride;
+    const uint8_t* color;      // frame 0's raw BGR image [Hc][Wc][3], frames color_stride bytes apart
+    int64_t color_stride;
+    uint32_t* zbuf;            // [n][Hc][Wc] scratch
+    uint16_t* reg;             // [n][Hc][Wc] registered depth (mm)
+    uint8_t* bgr;              // [n][H][W][3] colour registered to the depth
+    uint8_t* mask;             // [n][H][W] 1 = seen by the colour camera
+};
+// clear, splat, gather on the stream; ev (4 events) non-null: recorded before, between and after them
+hipError_t launch_depth_register(const DepthRegArgs& a, hipStream_t s, hipEvent_t* ev = nullptr);
 // dense-map outputs of the TSDF volume (k_dense.hip): marching-cubes mesh, capped exact ESDF
 struct DenseArgs {
     const float* tsdf;

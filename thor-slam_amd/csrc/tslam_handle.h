@@ -307,6 +307,22 @@ struct tslam_handle {
     tslam_stereo_depth_filter_params sd_flt_prm{};
     uint32_t* d_sd_label = nullptr;   // [sd_frames][H][W], with a speckle size only
     uint32_t* d_sd_count = nullptr;
+    // ---- tslam_api_register.cpp ----
+    // depth registration (tslam_depth_register_*), one state per pair: parameters (prm.map: the
+    // device copy of the table, or null), the z-buffer planes of one call and the output slots
+    struct DepthReg {
+        bool on = false;
+        tslam_depth_register_params prm{};
+        int frames = 0;                   // slots
+        int32_t* d_map = nullptr;         // [Hc][Wc][2]
+        uint32_t* d_z = nullptr;          // [frames][Hc][Wc]
+        uint16_t* d_reg = nullptr;        // [frames][Hc][Wc]
+        uint8_t* d_bgr = nullptr;         // [frames][H][W][3]
+        uint8_t* d_mask = nullptr;        // [frames][H][W]
+    } dr[8];
+    // tslam_depth_register_profile: events around the three passes of the newest call
+    bool dr_prof = false, dr_timed = false;
+    hipEvent_t dr_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     // ---- tslam_api_dense.cpp ----
     // dense-map outputs (tslam_mesh_* / tslam_esdf_*): scratch sized on first use
     uint8_t* d_mesh_cfg = nullptr;    // [cubes] configuration bytes
@@ -418,6 +434,9 @@ TSLAM_INTERNAL TsdfArgs integrate_args(const tslam_handle* h, const PairCamera& 
 TSLAM_INTERNAL TsdfFollowCall follow_call(const tslam_handle* h);
 // the fields of a that describe the volume: tsdf, weight, dims, origin, s, win (the colour layer is the caller's)
 TSLAM_INTERNAL void volume_view(const tslam_handle* h, TsdfRenderArgs& a);
+
+// -- tslam_api_register.cpp ------------------------------------------------------------------------
+TSLAM_INTERNAL void register_destroy(tslam_handle* h);   // its events (the buffers go with the handle's)
 
 // -- tslam_api_render.cpp --------------------------------------------------------------------------
 TSLAM_INTERNAL void align_off(tslam_handle* h);   // the align state belongs to the volume it was made for

@@ -134,6 +134,24 @@ class TsdfRenderParams(ctypes.Structure):
     ]
 
 
+class DepthRegisterParams(ctypes.Structure):
+    """tslam_depth_register_params: the rule of ``Handle.depth_register`` (thor_slam_amd/depth_register.py)."""
+    _fields_ = [
+        ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("color_width", ctypes.c_int32),
+        ("color_height", ctypes.c_int32), ("f_c", ctypes.c_double), ("cxc", ctypes.c_double), ("cyc", ctypes.c_double),
+        ("map", ctypes.c_void_p), ("color_T_rect", ctypes.c_double * 12), ("max_depth_mm", ctypes.c_int32),
+        ("tol_mm", ctypes.c_int32), ("max_splat", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ]
+
+
+class TsdfRigColor(ctypes.Structure):
+    """tslam_tsdf_rig_color: one camera's colour and mask of ``Handle.tsdf_integrate_rig_color``."""
+    _fields_ = [
+        ("color", ctypes.c_void_p), ("color_stride", ctypes.c_int64), ("mask", ctypes.c_void_p),
+        ("mask_stride", ctypes.c_int64),
+    ]
+
+
 class TsdfAlignParams(ctypes.Structure):
     """tslam_tsdf_align_params: the rule of ``Handle.tsdf_align`` (thor_slam_amd/dense_align.py)."""
     _fields_ = [
@@ -344,6 +362,21 @@ _SIGNATURES = {
                                                 ctypes.POINTER(ctypes.c_void_p)]),
     "tslam_tsdf_integrate_aligned": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                                     ctypes.c_int, ctypes.c_void_p]),
+    "tslam_depth_register_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]),
+    "tslam_depth_register": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                            ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "tslam_depth_register_blank": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "tslam_depth_register_buffers": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+                                                    ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                                    ctypes.c_void_p]),
+    "tslam_depth_register_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p]),
+    "tslam_depth_register_profile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "tslam_tsdf_integrate_rect_color": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                                       ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                                       ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "tslam_tsdf_integrate_rig_color": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                      ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 
@@ -1116,6 +1149,108 @@ class Handle:
         _check(self.lib.tslam_tsdf_integrate_aligned(self.h, ctypes.c_void_p(color_dev_ptr) if color_dev_ptr else None,
                                                      ctypes.c_void_p(depth_dev_ptr), int(stride_bytes), int(n_frames),
                                                      ctypes.c_void_p(stream)))
+
+    # -- depth registration (thor_slam_amd/depth_register.py) ------------------------------------
+    def depth_register_init(self, color_width: int, color_height: int, f_c: float, cxc: float, cyc: float, color_T_rect,
+                            map: np.ndarray | None = None, width: int | None = None, height: int | None = None,
+                            max_depth_mm: int = 65535, tol_mm: int = 50, max_splat: int = 4, max_frames: int = 1,
+                            pair: int = 0) -> None:
+        """The colour camera of ``pair`` (undistorted pinhole ``f_c, cxc, cyc``, the table ``map`` i32
+        [Hc][Wc][2] or None, ``color_T_rect`` 12 values), the depth image's size (default: the
+        handle's), the rule's parameters and the output slots of ``depth_register``."""
+        T = np.ascontiguousarray(color_T_rect, dtype=np.float64).reshape(-1)
+        if T.size != 12:
+            raise ValueError("color_T_rect must hold 12 values (3 x 4, row-major)")
+        width = self.width if width is None else int(width)
+        height = self.height if height is None else int(height)
+        mp = None
+        if map is not None:
+            mp = np.ascontiguousarray(map, dtype=np.int32)
+            if mp.shape != (int(color_height), int(color_width), 2):
+                raise ValueError(f"map must be {(int(color_height), int(color_width), 2)}")
+        prm = DepthRegisterParams(width, height, int(color_width), int(color_height), float(f_c), float(cxc), float(cyc),
+                                  None if mp is None else mp.ctypes.data, (ctypes.c_double * 12)(*[float(v) for v in T]),
+                                  int(max_depth_mm), int(tol_mm), int(max_splat), 0)
+        _check(self.lib.tslam_depth_register_init(self.h, int(pair), ctypes.addressof(prm), int(max_frames)))
+        if not hasattr(self, "_dr_shape"):
+            self._dr_shape = {}
+        self._dr_shape[int(pair)] = (height, width, int(color_height), int(color_width))
+
+    def depth_register(self, depth_dev_ptr: int, depth_stride: int, color_dev_ptr: int, color_stride: int, n_frames: int,
+                       first_slot: int = 0, pair: int = 0, stream: int = 0) -> None:
+        """n frames of device depth (u16 mm) and raw BGR colour planes into slots first_slot .. on the
+        stream (asynchronous); the other slots keep their contents."""
+        _check(self.lib.tslam_depth_register(self.h, int(pair), ctypes.c_void_p(depth_dev_ptr), int(depth_stride),
+                                             ctypes.c_void_p(color_dev_ptr), int(color_stride), int(n_frames),
+                                             int(first_slot), ctypes.c_void_p(stream)))
+
+    def depth_register_blank(self, n_frames: int, first_slot: int = 0, pair: int = 0, stream: int = 0) -> None:
+        """Zero ``bgr`` and ``mask`` of slots first_slot .. on the stream (frames without a colour
+        image); their registered depth keeps its contents."""
+        _check(self.lib.tslam_depth_register_blank(self.h, int(pair), int(n_frames), int(first_slot), ctypes.c_void_p(stream)))
+
+    def depth_register_buffers(self, pair: int = 0) -> tuple[dict, dict]:
+        """(device pointers, bytes of one slot) of ``depth`` (registered), ``bgr`` and ``mask``."""
+        names = ("depth", "bgr", "mask")
+        ptrs = [ctypes.c_void_p() for _ in names]
+        nbytes = (ctypes.c_int64 * 3)()
+        _check(self.lib.tslam_depth_register_buffers(self.h, int(pair), *[ctypes.byref(p) for p in ptrs],
+                                                     ctypes.addressof(nbytes)))
+        return {k: int(p.value or 0) for k, p in zip(names, ptrs)}, {k: int(b) for k, b in zip(names, nbytes)}
+
+    def depth_register_read(self, slot: int = 0, pair: int = 0) -> dict:
+        """One slot (synchronises): ``depth`` u16 [Hc][Wc] (mm, in the undistorted colour camera),
+        ``bgr`` u8 [H][W][3] and ``mask`` u8 [H][W] (registered to the depth)."""
+        shape = getattr(self, "_dr_shape", {}).get(int(pair))
+        if shape is None:   # no depth_register_init for the pair yet: the library says so
+            _check(self.lib.tslam_depth_register_read(self.h, int(pair), int(slot), None, None, None))
+            raise RuntimeError("depth_register_read without depth_register_init through this Handle")
+        H, W, Hc, Wc = shape
+        out = {"depth": np.zeros((Hc, Wc), np.uint16), "bgr": np.zeros((H, W, 3), np.uint8), "mask": np.zeros((H, W), np.uint8)}
+        _check(self.lib.tslam_depth_register_read(self.h, int(pair), int(slot), out["depth"].ctypes.data, out["bgr"].ctypes.data,
+                                                  out["mask"].ctypes.data))
+        return out
+
+    def depth_register_profile(self, enable: bool = True, read: bool = False) -> dict | None:
+        """Time the three passes of every later ``depth_register`` call; ``read``: the newest timed
+        call's times in ms first (waits for it)."""
+        ms = (ctypes.c_double * 3)()
+        _check(self.lib.tslam_depth_register_profile(self.h, int(bool(enable)), ctypes.addressof(ms) if read else None))
+        return dict(zip(("clear", "splat", "gather"), ms)) if read else None
+
+    def tsdf_integrate_rect_color(self, color_dev_ptr: int, color_stride: int, mask_dev_ptr: int | None, mask_stride: int,
+                                  depth_dev_ptr: int, stride_bytes: int, n_frames: int, first_frame: int = 0,
+                                  world_T_cam: np.ndarray | None = None, pair: int = 0, stream: int = 0) -> None:
+        """``tsdf_integrate_rect`` with BGR colour [H][W][3] (frames ``color_stride`` apart) and a
+        visibility mask u8 [H][W] (``mask_stride`` apart; None: every pixel): what ``depth_register``
+        writes.  The colour layer is updated only where the mask is non-zero."""
+        poses = None
+        if world_T_cam is not None:
+            poses = np.ascontiguousarray(np.asarray(world_T_cam, dtype=np.float64).reshape(-1, 4, 4))
+        _check(self.lib.tslam_tsdf_integrate_rect_color(
+            self.h, int(pair), ctypes.c_void_p(color_dev_ptr) if color_dev_ptr else None, int(color_stride),
+            ctypes.c_void_p(mask_dev_ptr) if mask_dev_ptr else None, int(mask_stride), ctypes.c_void_p(depth_dev_ptr),
+            int(stride_bytes), int(n_frames), int(first_frame), None if poses is None else poses.ctypes.data,
+            ctypes.c_void_p(stream)))
+
+    def tsdf_integrate_rig_color(self, cams, n_frames: int, first_frame: int = 0, world_T_base: np.ndarray | None = None,
+                                 stream: int = 0) -> None:
+        """``tsdf_integrate_rig`` where every camera's dict also has ``color`` (device pointer, BGR
+        [H][W][3]), ``color_stride``, and optionally ``mask`` (device pointer, u8 [H][W]) with
+        ``mask_stride``: colour with strides of its own, updated only where the mask is non-zero."""
+        arr = (TsdfRigCamera * max(len(cams), 1))()
+        col = (TsdfRigColor * max(len(cams), 1))()
+        for i, c in enumerate(cams):
+            arr[i] = TsdfRigCamera(int(c["pair"]), int(bool(c.get("rect", False))), int(c["depth"]) or None, None,
+                                   int(c["stride_bytes"]))
+            col[i] = TsdfRigColor(int(c.get("color") or 0) or None, int(c.get("color_stride", 0)),
+                                  int(c.get("mask") or 0) or None, int(c.get("mask_stride", 0)))
+        poses = None
+        if world_T_base is not None:
+            poses = np.ascontiguousarray(np.asarray(world_T_base, dtype=np.float64).reshape(-1, 4, 4))
+        _check(self.lib.tslam_tsdf_integrate_rig_color(self.h, ctypes.addressof(arr), ctypes.addressof(col), len(cams),
+                                                       int(n_frames), int(first_frame),
+                                                       None if poses is None else poses.ctypes.data, ctypes.c_void_p(stream)))
 
     # -- dense stereo depth (thor_slam_amd/stereo_depth.py) ------------------------------------
     def stereo_depth_init(self, max_frames: int = 1, n_disp: int = 0, uniqueness: int = 10, lr_tol: int = 1) -> None:

@@ -198,6 +198,17 @@ class HipSlamConfig(SlamConfig):
     stereo_depth_median: int = 0
     stereo_depth_speckle_size: int = 0
     stereo_depth_speckle_range: int = 32
+    # colour for a stereo rig's dense map (thor_slam_amd/depth_register.py): the source's colour
+    # camera (HipSlamEngine.set_color_camera / push_color, out of band as the reference's RGB-D
+    # stream) is registered to pair 0's stereo depth (with dense_cameras: to every selected pair
+    # that has a colour camera) and feeds the colour layer, with a mask where a nearer surface hides
+    # a depth pixel from the colour camera.  stereo_color_tol_m: how far behind the nearest surface a
+    # pixel still counts as seen (None = one voxel).  A colour image further than
+    # stereo_color_max_dt seconds from its frame (the reference's rgbd_sync_threshold_ms = 50), or
+    # none, leaves the colour layer alone for that frame.  Needs stereo_depth and dense_map.
+    stereo_color: bool = False
+    stereo_color_tol_m: float | None = None
+    stereo_color_max_dt: float = 0.05
     # pipeline
     batch_size: int = 1             # frames per submission
     sync: bool = False              # wait for every batch before process_frames returns (latency mode)
@@ -247,6 +258,21 @@ class HipSlamConfig(SlamConfig):
         check_stereo_depth_filter_params(self.stereo_depth_median, self.stereo_depth_speckle_size, self.stereo_depth_speckle_range)
         if (self.stereo_depth_median or self.stereo_depth_speckle_size) and not self.stereo_depth:
             raise ValueError("stereo_depth_median / stereo_depth_speckle_size need stereo_depth=True")
+        if self.stereo_color:
+            if not (self.stereo_depth and self.dense_map):
+                raise ValueError("stereo_color needs stereo_depth=True and dense_map=True")
+            if self.rgbd:
+                raise ValueError("stereo_color is for stereo rigs (rgbd=True already has colour)")
+            if self.devices:
+                raise ValueError("stereo_color does not run on a sharded rig (devices)")
+            if self.dense_align:
+                raise ValueError("stereo_color does not run with dense_align: aligned integration of coloured "
+                                 "stereo depth is not built")
+            if self.stereo_color_tol_m is not None and not (
+                    isinstance(self.stereo_color_tol_m, (int, float)) and 0 <= self.stereo_color_tol_m <= 65.535):
+                raise ValueError("stereo_color_tol_m must be None or a distance in [0, 65.535] m")
+            if not (isinstance(self.stereo_color_max_dt, (int, float)) and self.stereo_color_max_dt >= 0):
+                raise ValueError("stereo_color_max_dt must be >= 0")
         if self.dense_map:
             if not (self.rgbd or self.stereo_depth):
                 raise ValueError("dense_map needs depth: rgbd=True (depth input) or stereo_depth=True (stereo rig)")

@@ -35,7 +35,11 @@ in one launch per batch (``tslam_tsdf_integrate_rig``) on the rig's body poses, 
 and for dense stereo depth alike (``thor_slam_amd/dense_rig.py``).  ``dense_follow`` lets the volume
 follow the camera in whole voxels, decided on the device once per integrated batch
 (``thor_slam_amd/dense_follow.py``); ``get_dense_map`` / ``get_esdf`` / ``get_esdf_slice`` then
-report the window's effective ``origin`` and its ``window_shift``.
+report the window's effective ``origin`` and its ``window_shift``.  ``stereo_color`` colours a
+stereo rig's dense map from the source's centre colour camera (``thor_slam_amd/depth_register.py``):
+``set_color_camera`` after ``initialize``, ``push_color`` before the ``process_frames`` call of the
+frame the image belongs to; the colour is registered to the stereo depth on the device, and
+``get_registered_depth`` returns the depth aligned to the colour camera.
 With ``HipSlamConfig(devices=[d0, d1, ...])`` the rig is sharded one camera stream per GPU from
 this one process (cuVSLAM's multicam mode, launch/thor_visual_slam.launch.py:49,81):
 one handle per device, driven by the library as one sharded rig (``tslam_group_*``: an RCCL clique
@@ -69,6 +73,7 @@ from ..calib import (StereoRectification, confidence_from_covariance, extract_ca
                      stereo_pairs, stereo_rectify)
 from ..camera.rig import RigCalibration
 from ..dense_render import check_render_params, scaled_intrinsics, view_in_volume
+from ..depth_register import DEFAULT_MAX_SPLAT, check_register_params, color_camera, compose_color_T_rect
 from ..dense_rig import DenseCamerasError, resolve_dense_cameras
 from ..loop import span_edges
 from ..camera.types import SynchronizedFrameSet
@@ -461,6 +466,12 @@ class HipSlamEngine(SlamEngine):
         self._shard: dict | None = None           # sharded rig (config.devices): handles, group, inputs
         self._sd_last: dict = {}                  # pair -> (slot, timestamp) of its newest stereo depth image
         self._dense_pairs: tuple = ()             # config.dense_cameras resolved (() = pair 0 on its own pose)
+        # stereo_color: pair -> its colour camera (set_color_camera): pinned staging and device images
+        # per batch slot, per slot whether a colour image in time was pushed, the timestamp of a
+        # pushed image that waits for its frame; the newest registered frame (slot, timestamp) per pair
+        self._color_cams: dict = {}
+        self._color_zero: dict | None = None
+        self._reg_last: dict = {}
 
     # ------------------------------------------------------------------------------------------
     def initialize(self, calibration: RigCalibration, config: SlamConfig | None = None) -> None:
@@ -544,6 +555,7 @@ class HipSlamEngine(SlamEngine):
                         self._handle.stereo_depth_filter(median=cfg.stereo_depth_median, speckle_size=cfg.stereo_depth_speckle_size,
                                                          speckle_range=cfg.stereo_depth_speckle_range)
             self._sd_last = {}
+            self._color_cams, self._color_zero, self._reg_last = {}, None, {}
             self._view_key = None   # get_dense_view's camera (size, intrinsics, range) on the handle
             self._loop = None
             if cfg.enable_loop_closure and cfg.devices and cfg.rgbd:
@@ -697,8 +709,14 @@ class HipSlamEngine(SlamEngine):
         else:
             imgs = self._frame_images(frame_set)
         if imgs is None:
+            for cc in self._color_cams.values():
+                cc["pushed"] = None
             with self._pose_lock:
                 return self._latest_pose
+        for cc in self._color_cams.values():   # the colour pushed for this frame counts when it is in time
+            ts, cc["pushed"] = cc["pushed"], None
+            cc["has"][len(self._staged)] = (ts is not None and
+                                             abs(ts - float(frame_set.timestamp)) <= self._config.stereo_color_max_dt)
         self._staged.append((imgs, float(frame_set.timestamp)))
         self._staged_imu.append(self._imu_of(frame_set))
         if len(self._staged) >= self._config.batch_size:
@@ -737,7 +755,13 @@ class HipSlamEngine(SlamEngine):
             stream = torch.cuda.current_stream(self._device)
             self._dev_images[:n].copy_(self._host_images[:n], non_blocking=True)
             self._handle.submit(self._dev_images.data_ptr(), n, stream.cuda_stream)
-            self._integrate_depth(self._dev_images.data_ptr(), n, stream.cuda_stream, stamps=stamps)
+            has_color = {}
+            for p, cc in self._color_cams.items():   # the batch's colour images, and which slots hold one
+                has_color[p] = list(cc["has"][:n])
+                cc["has"] = [False] * len(cc["has"])
+                if any(has_color[p]):
+                    cc["dev"][:n].copy_(cc["host"][:n], non_blocking=True)
+            self._integrate_depth(self._dev_images.data_ptr(), n, stream.cuda_stream, stamps=stamps, has_color=has_color)
             self._staged, self._staged_imu = [], []
             self._prev_stamp = stamps[-1]
             self._publish(self._read(n), stamps, self._handle.frames_done - n)
@@ -940,7 +964,8 @@ class HipSlamEngine(SlamEngine):
 
     def process_batch(self, images, timestamps: list[float] | None = None, stream=None) -> dict:
         """Throughput entry: ``images`` is a device uint8 tensor already in HBM: [n, 2P, H, W] gray
-        stereo pairs, or [n, P, 5*H*W] RGB-D records (``rgbd.pack_rgbd``)."""
+        stereo pairs, or [n, P, 5*H*W] RGB-D records (``rgbd.pack_rgbd``).  No colour images come with
+        a device batch: with ``stereo_color`` its frames are integrated for their geometry only."""
         if self._handle is None:
             raise RuntimeError("Not initialized")
         if self._shard is not None:
@@ -958,18 +983,116 @@ class HipSlamEngine(SlamEngine):
     @property
     def _dense_color(self) -> bool:
         """The colour layer needs colour input: a stereo rig's images are gray, so ``dense_color``
-        is ignored with ``stereo_depth``."""
-        return self._config.dense_color and not self._config.stereo_depth
+        is ignored with ``stereo_depth``, unless the rig's colour camera is used (``stereo_color``)."""
+        return (self._config.dense_color and not self._config.stereo_depth) or self._config.stereo_color
+
+    # -- the colour camera of a stereo rig (thor_slam_amd/depth_register.py) ----------------------
+    def _color_pair(self, pair_or_source_name) -> int:
+        if isinstance(pair_or_source_name, str):
+            names = [self._cameras[l].source_name for l, _ in self._pairs]
+            if pair_or_source_name not in names:
+                raise ValueError(f"no stereo pair of source {pair_or_source_name!r}")
+            return names.index(pair_or_source_name)
+        p = int(pair_or_source_name)
+        if not 0 <= p < len(self._pairs):
+            raise ValueError(f"pair {p} out of range")
+        return p
+
+    def set_color_camera(self, pair_or_source_name, intrinsics, left_T_color) -> None:
+        """The colour camera of a stereo pair (``stereo_color``), after ``initialize`` and before
+        the first frame: its ``Intrinsics`` (the reference's ``get_rgbd_intrinsics()[0]``) and its
+        pose in the pair's left camera, ``left_T_color`` as ``Extrinsics`` (the inverse of
+        ``get_rgbd_extrinsics()[1]``).  Only pair 0's, or with ``dense_cameras`` a selected pair's,
+        feeds the map."""
+        cfg = self._config
+        if self._handle is None:
+            raise RuntimeError("Not initialized")
+        if not cfg.stereo_color:
+            raise RuntimeError("set_color_camera needs stereo_color=True")
+        if self._frame_count or self._staged:
+            raise RuntimeError("set_color_camera comes before the first frame")
+        p = self._color_pair(pair_or_source_name)
+        r = self._rects[p]
+        ccam = color_camera(intrinsics)
+        T = compose_color_T_rect(left_T_color.to_4x4_matrix(), r.left_optical_T_rect())
+        tol = cfg.voxel_size if cfg.stereo_color_tol_m is None else cfg.stereo_color_tol_m
+        tol_mm = int(math.floor(tol * 1000.0 + 0.5))
+        check_register_params(int(r.width), int(r.height), ccam["width"], ccam["height"], ccam["f_c"], ccam["cxc"],
+                              ccam["cyc"], T, tol_mm=tol_mm, max_frames=cfg.batch_size)
+        self._handle.depth_register_init(ccam["width"], ccam["height"], ccam["f_c"], ccam["cxc"], ccam["cyc"], T,
+                                         map=ccam["map"], tol_mm=tol_mm, max_splat=DEFAULT_MAX_SPLAT,
+                                         max_frames=cfg.batch_size, pair=p)
+        torch = self._torch
+        shape = (cfg.batch_size, ccam["height"], ccam["width"], 3)
+        self._color_cams[p] = {"shape": shape[1:], "host": torch.empty(shape, dtype=torch.uint8).pin_memory(),
+                               "dev": torch.zeros(shape, dtype=torch.uint8, device=f"cuda:{self._device}"),
+                               "has": [False] * cfg.batch_size, "pushed": None}
+        if self._color_zero is None:
+            # what a camera without a colour camera is integrated with: a zero mask and a black image
+            dev = f"cuda:{self._device}"
+            self._color_zero = {"mask": torch.zeros((cfg.batch_size, r.height, r.width), dtype=torch.uint8, device=dev),
+                                "bgr": torch.zeros((cfg.batch_size, r.height, r.width, 3), dtype=torch.uint8, device=dev)}
+
+    def push_color(self, pair_or_source_name, bgr: np.ndarray, timestamp: float) -> None:
+        """The colour camera's BGR image of the frame the next ``process_frames`` call brings, into
+        the pinned staging of that frame's batch slot.  An image further than
+        ``stereo_color_max_dt`` from its frame's timestamp is not used."""
+        p = self._color_pair(pair_or_source_name)
+        cc = self._color_cams.get(p)
+        if cc is None:
+            raise RuntimeError(f"pair {p} has no colour camera (set_color_camera)")
+        img = np.asarray(bgr)
+        if img.shape != cc["shape"] or img.dtype != np.uint8:
+            raise ValueError(f"colour image {img.shape} {img.dtype} does not match its calibration {cc['shape']} uint8")
+        np.copyto(cc["host"].numpy()[len(self._staged)], img)
+        cc["pushed"] = float(timestamp)
+
+    def _register_color(self, p: int, depth_ptr: int, frame_bytes: int, k0: int, m: int, has: list, stream: int,
+                        stamps: list | None) -> dict:
+        """Pair p's colour registered to the m depth frames at ``depth_ptr`` (batch slots k0 ..), into
+        registration slots 0 .. m - 1; the slots of frames without a colour image get a zero mask and
+        keep their registered depth, so the newest registered frame (``_reg_last``) stays readable
+        until a newer one is registered.  Returns the colour part of the pair's integrate call."""
+        cc = self._color_cams[p]
+        cbytes = int(np.prod(cc["shape"]))
+        j = 0
+        while j < m:
+            e = j
+            while e < m and has[k0 + e] == has[k0 + j]:
+                e += 1
+            if has[k0 + j]:
+                self._handle.depth_register(depth_ptr + j * frame_bytes, frame_bytes, cc["dev"].data_ptr() + (k0 + j) * cbytes,
+                                            cbytes, e - j, first_slot=j, pair=p, stream=stream)
+                self._reg_last[p] = (e - 1, None if stamps is None else float(stamps[k0 + e - 1]))
+            else:
+                self._handle.depth_register_blank(e - j, first_slot=j, pair=p, stream=stream)
+            j = e
+        ptrs, nbytes = self._handle.depth_register_buffers(p)
+        return dict(color=ptrs["bgr"], color_stride=nbytes["bgr"], mask=ptrs["mask"], mask_stride=nbytes["mask"])
+
+    def get_registered_depth(self, pair: int = 0) -> tuple | None:
+        """(depth u16 [Hc][Wc] in mm in pair ``pair``'s undistorted colour camera, timestamp) of the
+        newest frame whose stereo depth was registered to a colour image (``stereo_color``), or
+        None.  Synchronises."""
+        if self._handle is None or not self._config.stereo_color:
+            return None
+        self.flush()
+        if int(pair) not in self._reg_last:
+            return None
+        slot, stamp = self._reg_last[int(pair)]
+        return self._handle.depth_register_read(slot, int(pair))["depth"], stamp
 
     def _integrate_depth(self, records_ptr: int, n: int, stream: int, cams_per_frame: int | None = None,
-                         stamps: list | None = None) -> None:
+                         stamps: list | None = None, has_color: dict | None = None) -> None:
         """The batch's depth images of pair 0 into the TSDF volume, with the batch's device-resident
         tracked poses (untracked frames are skipped), on the batch's stream.  ``cams_per_frame``: the
         records per frame of the buffer (a sharded rig: rank 0's cameras, pair 0 first).  With
         ``stereo_depth`` the depth of the batch's frames g with g % stereo_depth_interval == 0 is
         first computed from pair 0's rectified images (k_stereo_depth.hip), in the rectified camera.
         With ``dense_cameras`` the selected pairs' depth (records, or stereo depth in slots ci m ..)
-        goes in by one ``tsdf_integrate_rig`` per run of frames, on the rig's body poses."""
+        goes in by one ``tsdf_integrate_rig`` per run of frames, on the rig's body poses.  With
+        ``stereo_color``, ``has_color[pair]`` says which of the batch's frames came with a colour
+        image: the pair's colour is registered to its stereo depth and goes in with a mask."""
         if not self._config.dense_map:
             return
         dense = self._dense_pairs
@@ -979,12 +1102,25 @@ class HipSlamEngine(SlamEngine):
             depth_ptr, _, frame_bytes = self._handle.stereo_depth_buffers()
             # one launch per run of consecutive frames (the whole batch at interval 1)
             runs = [(g0, n)] if every == 1 else [(g, 1) for g in range(g0, g0 + n) if g % every == 0]
+            # has_color None (process_batch: no colour images come with a device batch): geometry only
+            colored = [] if has_color is None else [p for p in (dense or (0,)) if p in self._color_cams]
+            none = [False] * n
             for g, m in runs:
                 stamp = None if stamps is None else float(stamps[g + m - 1 - g0])
                 if dense:   # camera ci's run in slots ci m .., then every camera's views in one launch
                     for ci, p in enumerate(dense):
                         self._handle.stereo_depth(g, m, pair=p, stream=stream, first_slot=ci * m)
                         self._sd_last[p] = (ci * m + m - 1, stamp)
+                    if colored:   # a pair without a colour camera: a black image and a zero mask
+                        z, hw = self._color_zero, self._rects[0].width * self._rects[0].height
+                        blank = dict(color=z["bgr"].data_ptr(), color_stride=3 * hw, mask=z["mask"].data_ptr(), mask_stride=hw)
+                        self._handle.tsdf_integrate_rig_color(
+                            [dict(pair=p, rect=True, depth=depth_ptr + ci * m * frame_bytes, stride_bytes=frame_bytes,
+                                  **(self._register_color(p, depth_ptr + ci * m * frame_bytes, frame_bytes, g - g0, m,
+                                                          (has_color or {}).get(p, none), stream, stamps)
+                                     if p in colored else blank))
+                             for ci, p in enumerate(dense)], m, first_frame=g, stream=stream)
+                        continue
                     self._handle.tsdf_integrate_rig(
                         [dict(pair=p, rect=True, depth=depth_ptr + ci * m * frame_bytes, stride_bytes=frame_bytes)
                          for ci, p in enumerate(dense)], m, first_frame=g, stream=stream)
@@ -993,6 +1129,10 @@ class HipSlamEngine(SlamEngine):
                 if self._config.dense_align:   # aligned to the map first, integrated on the aligned poses
                     self._handle.tsdf_align(depth_ptr, frame_bytes, m, first_frame=g, stream=stream)
                     self._handle.tsdf_integrate_aligned(depth_ptr, frame_bytes, m, stream=stream)
+                elif colored:   # pair 0's colour registered to the depth, with its mask
+                    col = self._register_color(0, depth_ptr, frame_bytes, g - g0, m, (has_color or {}).get(0, none), stream, stamps)
+                    self._handle.tsdf_integrate_rect_color(col["color"], col["color_stride"], col["mask"], col["mask_stride"],
+                                                           depth_ptr, frame_bytes, m, first_frame=g, pair=0, stream=stream)
                 else:
                     self._handle.tsdf_integrate_rect(depth_ptr, frame_bytes, m, first_frame=g, pair=0, stream=stream)
                 self._sd_last[0] = (m - 1, stamp)
@@ -1530,6 +1670,9 @@ class HipSlamEngine(SlamEngine):
         self._kf_imu = None
         self._kf_ine = None
         self._sd_last = {}
+        self._reg_last = {}
+        for cc in self._color_cams.values():
+            cc["has"], cc["pushed"] = [False] * len(cc["has"]), None
         if self._imu is not None:
             self._imu.reset()
         self._keyframe_poses = []

@@ -390,6 +390,46 @@ class SyntheticRGBDSource(SyntheticStereoSource):
         return out
 
 
+class SyntheticStereoColorSource(SyntheticStereoSource):
+    """A stereo source that also renders its centre colour camera (CAM_A of the reference's rigs):
+    the two mono cameras as ``SyntheticStereoSource`` renders them, plus a colour camera between
+    them at ``color_offset`` of the baseline from the left camera (0.5 = the middle), with its own
+    size and optional distortion and the channel gains of ``SyntheticRGBDSource``.  Calibration and
+    frames of the colour camera come out of band, as the reference's RGB-D stream does:
+    ``get_rgbd_intrinsics`` / ``get_rgbd_extrinsics`` (luxonis.py:974-1091) and ``render_color``."""
+
+    def __init__(self, name: str = "192.168.2.21", color_width: int = 1280, color_height: int = 800,
+                 color_offset: float = 0.5, color_distortion: np.ndarray | None = None, **kw) -> None:
+        super().__init__(name=name, **kw)
+        self.color_intrinsics = default_intrinsics(color_width, color_height, color_distortion)
+        m = np.eye(4)
+        m[0, 3] = (color_offset - 0.5) * self.baseline   # the left camera sits at -baseline / 2
+        self._color_extr = Extrinsics.from_4x4_matrix(m)
+
+    def left_T_color(self) -> Extrinsics:
+        """The colour camera in the left camera's optical frame."""
+        return Extrinsics.from_4x4_matrix(np.linalg.inv(self._extr[0].to_4x4_matrix()) @ self._color_extr.to_4x4_matrix())
+
+    def get_rgbd_intrinsics(self) -> tuple[Intrinsics, Intrinsics]:
+        """(colour, depth): the depth lives in the left camera."""
+        return self.color_intrinsics, self._intr[0]
+
+    def get_rgbd_extrinsics(self) -> tuple[Extrinsics, Extrinsics]:
+        """(identity, color_T_left): the colour camera is the reference, as the reference's driver has it."""
+        return (Extrinsics.from_4x4_matrix(np.eye(4)),
+                Extrinsics.from_4x4_matrix(np.linalg.inv(self.left_T_color().to_4x4_matrix())))
+
+    def color_pose(self, i: int) -> np.ndarray:
+        """world_T_cam (RDF optical frame) of the colour camera at frame ``i``."""
+        return self.trajectory[i % len(self.trajectory)] @ self.rig_T_source @ self._color_extr.to_4x4_matrix()
+
+    def render_color(self, i: int, noise: bool = True) -> np.ndarray:
+        """The colour camera's BGR u8 [Hc][Wc][3] image of frame ``i``."""
+        rng = np.random.default_rng((self.seed, i, 2)) if noise else None
+        gf = self.scene.render(self.color_pose(i), self.color_intrinsics, rng).astype(np.float64)
+        return np.stack([np.clip(np.floor(0.8 * gf + 30.5), 0, 255), gf, np.clip(np.floor(1.1 * gf - 9.5), 0, 255)],
+                        axis=-1).astype(np.uint8)
+
 
 def synthetic_rgbd_rig(joints: dict, names: list[str] | tuple[str, ...], width: int = 1280, height: int = 720,
                        traj_len: int = 40, scene_seed: int = 0):
