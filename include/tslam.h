@@ -636,6 +636,14 @@ int tslam_match_mode(tslam_handle* h, int mode, int merge_cap);
  * positions, [4] blocks that matched; the rest 0.  blocks_per_cu (or null): the k_match blocks the runtime places on a
  * compute unit (4 with the merge array inside the kernel's LDS budget). */
 int tslam_match_counters(tslam_handle* h, uint32_t* counters16, int* blocks_per_cu);
+/* Round counters of the FAST / NMS detector (synchronises).  The first call switches to a counting
+ * build of the kernel and returns zeros; every call returns the counts since the previous one and
+ * clears them.  counters: [max_levels][12] (at most 6 levels are written), per level and stage
+ * (phase B bright 0..2, phase B dark 3..5, NMS 6..8) the rounds of 64 quads flushed inside the
+ * loop, the rounds on the queues' tails and the lanes those rounds filled (phase B pools the tails
+ * of a block's waves into rounds of 64; an NMS tail round is one wave's own); [9] the blocks that
+ * ran (the t + 1 fallback's included); the rest 0.  Results do not depend on counting. */
+int tslam_detect_counters(tslam_handle* h, uint32_t* counters, int max_levels);
 /* Measurement: `reps` back-to-back k_ba_schur launches on pair `pair`'s last solved window (the
  * kernel only rewrites its own outputs), between two HIP events on `stream`: the average launch
  * duration and the algorithmic flops per launch (for the FP64 MFMA roofline, without per-launch

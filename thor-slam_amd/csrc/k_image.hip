@@ -359,31 +359,26 @@ __device__ __forceinline__ uint32_t fast4_any(const uint8_t* rc, int W, int x0, 
     return ((~ab & 0x80008000u) != 0u ? 1u : 0u) | ((~ad & 0x80008000u) != 0u ? 2u : 0u);
 }
 
-// Phase B: exact scores (>= te, else 0) of the `cnt` (<= 64) candidate quads at q (entries
-// r << 9 | quad: score row r, columns 4 quad .. 4 quad + 3), one quad per lane with the dense
-// aligned-dword fast4s of one side, combined by a byte-wise max into the quad's score word (zeroed
-// by phase A; a quad with candidates on both sides is in both queues).  92 % of the candidate quads
-// have candidates on one side only, so splitting the queue by side skips half the arc work.
-// Wave-local (no block barrier).
+// Phase B: exact scores (>= te, else 0) of up to 64 candidate quads, one per lane (`on`: the lane
+// holds one; entry e = r << 9 | quad: score row r, columns 4 quad .. 4 quad + 3) with the dense
+// aligned-dword fast4s of one side, combined into the quad's score word (zeroed by phase A; a quad
+// with candidates on both sides is in both queues).  92 % of the candidate quads have candidates on
+// one side only, so splitting the queue by side skips half the arc work.  The two sides combine by
+// an LDS atomic OR: a pixel cannot have a 9-arc on both sides of a 16-circle, bytes below te are
+// zero and the word starts at zero, so OR is the byte-wise max, whichever wave scores the other
+// side (the pooled rounds deal a quad's two sides to any two waves).  No block barrier.
+#define TS_DET_THREADS 512
+#define TS_DET_WAVES (TS_DET_THREADS / 64)
 #define TS_DET_Q 128   // per-wave, per-side candidate queue (quads): flushed at 64, + <= 64 per append
 #ifndef TS_DET_U
 #define TS_DET_U 2     // phase-A items per lane per iteration: 2 / 3 / 4 -> 71 / 79 / 80+5 spilled VGPRs;
                        // 467 / 466 / 478 us alone, 931 / 957 / 978 us beside the back end, C2 bench
                        // 145.0k / 143.1k / 141.6k frames/s (round 2)
 #endif
-__device__ __forceinline__ uint32_t bytes_max(uint32_t a, uint32_t b) {
-    typedef unsigned short u16v2 __attribute__((ext_vector_type(2)));
-    const u16v2 ae = __builtin_bit_cast(u16v2, a & 0x00FF00FFu), ao = __builtin_bit_cast(u16v2, (a >> 8) & 0x00FF00FFu);
-    const u16v2 be = __builtin_bit_cast(u16v2, b & 0x00FF00FFu), bo = __builtin_bit_cast(u16v2, (b >> 8) & 0x00FF00FFu);
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(ae, be)) |
-           (__builtin_bit_cast(uint32_t, __builtin_elementwise_max(ao, bo)) << 8);
-}
 template <int SIDE>
-__device__ __forceinline__ void fast_flush(const uint16_t* q, int cnt, const uint8_t* tile, uint32_t* score32, int W,
-                                           int te, bool border) {
-    const int lane = threadIdx.x & 63;
-    if (lane >= cnt) return;
-    const uint32_t e = q[lane];
+__device__ __forceinline__ void fast_flush(uint32_t e, bool on, const uint8_t* tile, uint32_t* score32, int W, int te,
+                                           bool border) {
+    if (!on) return;
     const int r = (int)(e >> 9), x4 = (int)(e & 511u), x0 = 4 * x4;
     uint32_t sc4 = fast4s<SIDE>(tile + (r + TS_DET_HALO - 1) * W, W, x0, te - 1);
     if (border) {   // margin < 7 only: a quad may hold pixels outside [3, W-3)
@@ -393,15 +388,44 @@ __device__ __forceinline__ void fast_flush(const uint16_t* q, int cnt, const uin
             sc4 &= keep >= 4 ? 0xFFFFFFFFu : ((1u << (8 * keep)) - 1u);
         }
     }
-    uint32_t* w = score32 + r * (W >> 2) + x4;
-    *w = bytes_max(*w, sc4);
+    if (sc4) atomicOr(score32 + r * (W >> 2) + x4, sc4);
 }
 
-// 3x3 NMS of the `cnt` (<= 64) queued nonzero score quads at q (entries r << 9 | quad: score row
-// r = y - y0 + 1, pixels 4 quad .. 4 quad + 3), one quad per lane; survivors inside the margin
-// M <= x < W - M are appended to `cand` (one LDS atomic per wave) and counted in `hist`.
-// Wave-local (no block barrier).
-__device__ __forceinline__ void nms_flush(const uint16_t* q, int cnt, const uint32_t* sc32, int W4, int W, int M, int y0,
+// The tails of a block's queues, pooled.  A wave flushes 64 entries at a time inside its loop and is
+// left with fewer than 64 per queue; a round on such a tail issues every instruction of a full one
+// (mean fill 28 of 64 in phase B).  So the tails stay in the waves' queues (wave w's
+// at q + w * stride, tail[w] entries), a barrier publishes the eight counts, and the block's pooled
+// entries, the tails back to back, are dealt to the waves in rounds of 64.  pool_counts: the
+// wave-uniform prefix of the counts (in SGPRs); pooled_entry: entry j of the pool.
+struct TailPool {
+    int end[TS_DET_WAVES];   // entries of waves 0 .. w
+};
+__device__ __forceinline__ TailPool pool_counts(const uint32_t* tail) {
+    TailPool p;
+    int acc = 0;
+#pragma unroll
+    for (int w = 0; w < TS_DET_WAVES; ++w) {
+        acc += __builtin_amdgcn_readfirstlane((int)tail[w]);
+        p.end[w] = acc;
+    }
+    return p;
+}
+__device__ __forceinline__ uint32_t pooled_entry(const TailPool& p, const uint16_t* q, int stride, int j) {
+    int w = 0, first = 0;
+#pragma unroll
+    for (int k = 0; k + 1 < TS_DET_WAVES; ++k)
+        if (j >= p.end[k]) {
+            w = k + 1;
+            first = p.end[k];
+        }
+    return q[w * stride + (j - first)];
+}
+
+// 3x3 NMS of up to 64 queued nonzero score quads, one per lane (`on`: the lane holds one; entry
+// e = r << 9 | quad: score row r = y - y0 + 1, pixels 4 quad .. 4 quad + 3); survivors inside the
+// margin M <= x < W - M are appended to `cand` (one LDS atomic per wave) and counted in `hist`.
+// The whole wave calls it (ballots); no block barrier.
+__device__ __forceinline__ void nms_flush(uint32_t e, bool on, const uint32_t* sc32, int W4, int W, int M, int y0,
                                           uint32_t* cand, uint32_t* count, uint32_t* hist) {
     const int lane = threadIdx.x & 63;
     constexpr uint32_t k64 = 0x64646464u;
@@ -409,8 +433,7 @@ __device__ __forceinline__ void nms_flush(const uint16_t* q, int cnt, const uint
     uint32_t kbits = 0;   // bit j: pixel x0 + j survives
     uint32_t P = 0;
     int y = 0, x0 = 0;
-    if (lane < cnt) {
-        const uint32_t e = q[lane];
+    if (on) {
         const int r = (int)(e >> 9), qq = (int)(e & 511u);
         y = y0 - 1 + r;
         x0 = 4 * qq;
@@ -470,10 +493,8 @@ __device__ __forceinline__ void nms_flush(const uint16_t* q, int cnt, const uint
 // CU = the VGPR limit at 70 registers; 1.25x halo rows instead of 1.5x at BR = 16: 778 -> 725 us
 // per 256-frame batch), 24 at W = 1280 (74 KiB, 2 blocks per CU as at 16: 611 -> 575 us per
 // 50-frame C4 batch).  Work inside each phase is dealt
-// to the 8 waves in equal (row, 64-lane chunk) items.
+// to the 8 waves (TS_DET_WAVES, above) in equal (row, 64-lane chunk) items.
 // ---------------------------------------------------------------------------------------------
-#define TS_DET_THREADS 512
-#define TS_DET_WAVES (TS_DET_THREADS / 64)
 
 // 16-byte async global -> LDS copy; `wave_dst` is the wave-uniform LDS base, lane k lands at +16k
 __device__ __forceinline__ void glds16(const uint4* src, uint4* wave_dst) {
@@ -483,47 +504,31 @@ __device__ __forceinline__ void glds16(const uint4* src, uint4* wave_dst) {
 
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
-// Horizontal 1-4-6-4-1 of the 4 pixels x0..x0+3 of one tile row as two u16 pairs:
-// ev = (h[x0], h[x0+2]), od = (h[x0+1], h[x0+3]).  Byte windows D_k = row[x0-2+k .. x0+1+k].
-// Column clamp (x-2 < 0, x+2 > W-1) only for the first and last quad of a row.
-__device__ __forceinline__ void hsum4(const uint8_t* row, int x0, int W, u16x2* ev, u16x2* od) {
-    uint32_t D[5];
-    if (x0 >= 4 && x0 + 8 <= W) {
-        const uint32_t a = *(const uint32_t*)(row + x0 - 4), b = *(const uint32_t*)(row + x0),
-                       c2 = *(const uint32_t*)(row + x0 + 4);
-        D[0] = __builtin_amdgcn_alignbyte(b, a, 2);
-        D[1] = __builtin_amdgcn_alignbyte(b, a, 3);
-        D[2] = b;
-        D[3] = __builtin_amdgcn_alignbyte(c2, b, 1);
-        D[4] = __builtin_amdgcn_alignbyte(c2, b, 2);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            uint32_t w = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) w |= (uint32_t)row[min(max(x0 - 2 + k + j, 0), W - 1)] << (8 * j);
-            D[k] = w;
-        }
-    }
+// Horizontal 1-4-6-4-1 of the 4 pixels x0..x0+3 of one tile row (`p` = row + x0) as two u16 pairs:
+// ev = (h[x0], h[x0+2]), od = (h[x0+1], h[x0+3]).  Byte windows D_k = row[x0-2+k .. x0+1+k] of the
+// dwords a, b, c2 at p - 4, p, p + 4, each picked by one v_perm_b32 whose selector the lane holds:
+// an interior quad takes bytes of the neighbour dwords, the first quad of a row replicates byte 0
+// of b for the columns left of the image and the last one byte 3 for those right of it (the
+// column clamp; the neighbour dword it loads belongs to the row before / after and is ignored).
+// So the two edge quads of a row are items like any other, at no instruction more.
+struct HsumSel {
+    uint32_t d0, d1, d3, d4;
+};
+__device__ __forceinline__ HsumSel hsum_sel(bool first, bool last) {
+    return {first ? 0x05040404u : 0x05040302u, first ? 0x06050404u : 0x06050403u,
+            last ? 0x03030201u : 0x04030201u, last ? 0x03030302u : 0x05040302u};
+}
+__device__ __forceinline__ void hsum4(const uint8_t* p, const HsumSel& s, u16x2* ev, u16x2* od) {
+    const uint32_t a = *(const uint32_t*)(p - 4), b = *(const uint32_t*)p, c2 = *(const uint32_t*)(p + 4);
+    const uint32_t D0 = __builtin_amdgcn_perm(b, a, s.d0), D1 = __builtin_amdgcn_perm(b, a, s.d1);
+    const uint32_t D3 = __builtin_amdgcn_perm(c2, b, s.d3), D4 = __builtin_amdgcn_perm(c2, b, s.d4);
     // pixel x0 + j: taps row[x0-2+j .. x0+1+j] = bytes of D_j against weights (1, 4, 6, 4), plus
     // row[x0+2+j] = byte 3 of D_{j+1}: one v_dot4_u32_u8 with that byte as the accumulator
-    uint32_t hj[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) hj[j] = __builtin_amdgcn_udot4(D[j], 0x04060401u, D[j + 1] >> 24, false);
-    *ev = __builtin_bit_cast(u16x2, hj[0] | (hj[2] << 16));   // sums <= 16 * 255: u16 lanes
-    *od = __builtin_bit_cast(u16x2, hj[1] | (hj[3] << 16));
-}
-
-// Horizontal 1-4-6-4-1 of an interior quad (4 <= x0, x0 + 8 <= W: no column clamp), `p` = row + x0.
-__device__ __forceinline__ void hsum4_in(const uint8_t* p, u16x2* ev, u16x2* od) {
-    const uint32_t a = *(const uint32_t*)(p - 4), b = *(const uint32_t*)p, c2 = *(const uint32_t*)(p + 4);
-    const uint32_t D0 = __builtin_amdgcn_alignbyte(b, a, 2), D1 = __builtin_amdgcn_alignbyte(b, a, 3);
-    const uint32_t D3 = __builtin_amdgcn_alignbyte(c2, b, 1), D4 = __builtin_amdgcn_alignbyte(c2, b, 2);
     const uint32_t h0 = __builtin_amdgcn_udot4(D0, 0x04060401u, D1 >> 24, false);
     const uint32_t h1 = __builtin_amdgcn_udot4(D1, 0x04060401u, b >> 24, false);
     const uint32_t h2 = __builtin_amdgcn_udot4(b, 0x04060401u, D3 >> 24, false);
     const uint32_t h3 = __builtin_amdgcn_udot4(D3, 0x04060401u, D4 >> 24, false);
-    *ev = __builtin_bit_cast(u16x2, h0 | (h2 << 16));
+    *ev = __builtin_bit_cast(u16x2, h0 | (h2 << 16));   // sums <= 16 * 255: u16 lanes
     *od = __builtin_bit_cast(u16x2, h1 | (h3 << 16));
 }
 
@@ -541,12 +546,15 @@ __device__ __forceinline__ uint32_t vsum4(u16x2 e0, u16x2 e1, u16x2 e2, u16x2 e3
 // MODE 0: speculative threshold (k_detect); MODE 1: exact fallback at t + 1 for the flagged
 // images (k_detect_fallback, its own symbol so profiles keep the two launches apart)
 // (bx: the band over all levels, img: the view image; the fallback runs only flagged image-levels)
-template <int MODE>
+// CNT: the build that counts its flush rounds for tslam_detect_counters (k_detect_counted,
+// k_detect_fallback_counted); the shipped kernels hold none of that code
+template <int MODE, bool CNT>
 __device__ __forceinline__ void detect_body(const BatchCtx& c, int bx, int img) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     __shared__ uint32_t s_hist[256];
     __shared__ uint32_t s_count;
     __shared__ uint16_t s_q[TS_DET_WAVES][2][TS_DET_Q];   // per wave: bright, dark candidate quads
+    __shared__ __attribute__((aligned(16))) uint32_t s_tail[2][TS_DET_WAVES];   // the waves' phase-B tails (pooled rounds)
     int f, cam;
     view_image(c, img, &f, &cam);
     int l = 0;
@@ -600,30 +608,30 @@ __device__ __forceinline__ void detect_body(const BatchCtx& c, int bx, int img) 
 
     // 5x5 binomial smoothing of the band rows (column clamp; rows already clamped in LDS).
     if (wide) {
-        // item = (4-pixel quad, row group): the horizontal sums (3 dword LDS reads + 4 v_dot4
-        // each) slide through 5 register pairs, rotated by unrolling 5 rows (no moves); u16 pairs
-        // cannot overflow (16 * 16 * 255 + 128 < 2^16).  Interior quads (1 .. W4 - 2) need no
-        // column clamp and run without divergence; the two edge quads of each row group follow.
+        // item = (4-pixel quad, row group): the horizontal sums (3 dword LDS reads + 4 v_perm +
+        // 4 v_dot4 each) slide through 5 register pairs, rotated by unrolling 5 rows (no moves);
+        // u16 pairs cannot overflow (16 * 16 * 255 + 128 < 2^16).  The first and last quad of a
+        // row clamp their columns through the v_perm selectors (hsum4) and run in the same loop.
         const int W4 = W >> 2;
         const int groups = c.g.smooth_groups[l];
         const int SR = (BR + groups - 1) / groups;
-        const int NQ = W4 - 2;
-        for (int it = threadIdx.x; it < groups * NQ; it += TS_DET_THREADS) {
-            const int half = it / NQ, q = 1 + (it - half * NQ), x0 = 4 * q;
+        for (int it = threadIdx.x; it < groups * W4; it += TS_DET_THREADS) {
+            const int half = it / W4, q = it - half * W4, x0 = 4 * q;
             const int o0 = SR * half, o1 = min(o0 + SR, rows_here);   // output rows (band-relative)
             if (o0 >= o1) continue;
+            const HsumSel hs = hsum_sel(q == 0, q == W4 - 1);
             const uint8_t* rp = tile + (TS_DET_HALO - 2 + o0) * W + x0;
             u16x2 e0, e1, e2, e3, e4, d0, d1, d2, d3, d4;
-            hsum4_in(rp, &e0, &d0);
-            hsum4_in(rp + W, &e1, &d1);
-            hsum4_in(rp + 2 * W, &e2, &d2);
-            hsum4_in(rp + 3 * W, &e3, &d3);
+            hsum4(rp, hs, &e0, &d0);
+            hsum4(rp + W, hs, &e1, &d1);
+            hsum4(rp + 2 * W, hs, &e2, &d2);
+            hsum4(rp + 3 * W, hs, &e3, &d3);
             rp += 4 * W;
             uint32_t off = (uint32_t)((y0 + o0) * W + x0);
             int o = o0;
 #define TS_SMOOTH_ROW(A, B, C, D, N, a, b, cc, d, n)                            \
     {                                                                         \
-        hsum4_in(rp, &N, &n);                                                 \
+        hsum4(rp, hs, &N, &n);                                                \
         *(uint32_t*)(smo + off) = vsum4(A, B, C, D, N, a, b, cc, d, n);       \
         rp += W;                                                              \
         off += (uint32_t)W;                                                   \
@@ -637,23 +645,6 @@ __device__ __forceinline__ void detect_body(const BatchCtx& c, int bx, int img) 
                 TS_SMOOTH_ROW(e4, e0, e1, e2, e3, d4, d0, d1, d2, d3)
             }
 #undef TS_SMOOTH_ROW
-        }
-        for (int it = threadIdx.x; it < groups * 2; it += TS_DET_THREADS) {   // the edge quads (clamped)
-            const int half = it >> 1, x0 = (it & 1) ? 4 * (W4 - 1) : 0;
-            const int o0 = SR * half, o1 = min(o0 + SR, rows_here);
-            if (o0 >= o1) continue;
-            u16x2 e[5], d[5];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) hsum4(tile + (TS_DET_HALO - 2 + o0 + k) * W, x0, W, &e[k], &d[k]);
-            for (int o = o0; o < o1; ++o) {
-                hsum4(tile + (TS_DET_HALO + 2 + o) * W, x0, W, &e[4], &d[4]);
-                *(uint32_t*)(smo + (size_t)(y0 + o) * W + x0) = vsum4(e[0], e[1], e[2], e[3], e[4], d[0], d[1], d[2], d[3], d[4]);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    e[k] = e[k + 1];
-                    d[k] = d[k + 1];
-                }
-            }
         }
     } else {
         for (int x = threadIdx.x; x < W; x += TS_DET_THREADS) {
@@ -693,6 +684,7 @@ __device__ __forceinline__ void detect_body(const BatchCtx& c, int bx, int img) 
         uint16_t* qb = s_q[wave][0];
         uint16_t* qd = s_q[wave][1];
         int nqb = 0, nqd = 0;   // wave-uniform
+        uint32_t cnt_b = 0, cnt_d = 0;   // CNT: in-loop rounds
         const int nitems = max(rb - ra, 0) * nq;
         // (row, quad) of item it = wave * 64 + lane + k * TS_DET_THREADS, stepped without a division;
         // TS_DET_U items per lane per iteration, so their 5 LDS reads each are in flight together
@@ -730,7 +722,7 @@ __device__ __forceinline__ void detect_body(const BatchCtx& c, int bx, int img) 
                         cb[u] = (c4 & 0xFu) != 0;
                         cd[u] = (c4 >> 4) != 0;
                     }
-                    score32[ru[u] * W4 + xu[u]] = 0;   // the flushes max their scores into it
+                    score32[ru[u] * W4 + xu[u]] = 0;   // the flushes OR their scores into it
                 }
             }
 #pragma unroll
@@ -744,17 +736,50 @@ __device__ __forceinline__ void detect_body(const BatchCtx& c, int bx, int img) 
                 // a wave's LDS operations complete in issue order, and the queues are wave-private:
                 // no fence between its entries' stores and the flush's loads
                 if (nqb >= 64) {
-                    fast_flush<1>(qb + nqb - 64, 64, tile, score32, W, te, border);
                     nqb -= 64;
+                    fast_flush<1>(qb[nqb + lane], true, tile, score32, W, te, border);
+                    if (CNT) ++cnt_b;
                 }
                 if (nqd >= 64) {
-                    fast_flush<2>(qd + nqd - 64, 64, tile, score32, W, te, border);
                     nqd -= 64;
+                    fast_flush<2>(qd[nqd + lane], true, tile, score32, W, te, border);
+                    if (CNT) ++cnt_d;
                 }
             }
         }
-        if (nqb > 0) fast_flush<1>(qb, nqb, tile, score32, W, te, border);
-        if (nqd > 0) fast_flush<2>(qd, nqd, tile, score32, W, te, border);
+        // the tails (entries 0 .. nqb-1, 0 .. nqd-1 of the wave's queues) pooled over the block:
+        // bright rounds first, then dark ones, round k to wave k % 8
+        if (lane == 0) {
+            s_tail[0][wave] = (uint32_t)nqb;
+            s_tail[1][wave] = (uint32_t)nqd;
+        }
+        __syncthreads();
+        const TailPool pb = pool_counts(s_tail[0]), pd = pool_counts(s_tail[1]);
+        const int totb = pb.end[TS_DET_WAVES - 1], totd = pd.end[TS_DET_WAVES - 1];
+        const int rndb = (totb + 63) >> 6, rndd = (totd + 63) >> 6;
+        for (int k = wave; k < rndb + rndd; k += TS_DET_WAVES) {   // wave-uniform
+            if (k < rndb) {
+                const int j = 64 * k + lane;
+                const bool on = j < totb;
+                fast_flush<1>(on ? pooled_entry(pb, s_q[0][0], 2 * TS_DET_Q, j) : 0u, on, tile, score32, W, te, border);
+            } else {
+                const int j = 64 * (k - rndb) + lane;
+                const bool on = j < totd;
+                fast_flush<2>(on ? pooled_entry(pd, s_q[0][1], 2 * TS_DET_Q, j) : 0u, on, tile, score32, W, te, border);
+            }
+        }
+        if (CNT) {
+            uint32_t* dc = c.det_cnt + l * TS_DCNT;
+            if (lane == 0 && cnt_b) atomicAdd(&dc[0], cnt_b);
+            if (lane == 0 && cnt_d) atomicAdd(&dc[3], cnt_d);
+            if (threadIdx.x == 0) {
+                atomicAdd(&dc[1], (uint32_t)rndb);
+                atomicAdd(&dc[2], (uint32_t)totb);
+                atomicAdd(&dc[4], (uint32_t)rndd);
+                atomicAdd(&dc[5], (uint32_t)totd);
+                atomicAdd(&dc[TS_DCNT_BLOCKS], 1u);
+            }
+        }
     } else {
         for (int i = threadIdx.x; i < (BR + 2) * W; i += TS_DET_THREADS) {
             const int r = i / W, x = i - r * W;
@@ -786,6 +811,7 @@ __device__ __forceinline__ void detect_body(const BatchCtx& c, int bx, int img) 
         const uint32_t* sc32 = (const uint32_t*)score;
         uint16_t* nq = s_q[wave][0];   // 2 * TS_DET_Q contiguous entries: phase B is done (barrier)
         int nn = 0;                    // wave-uniform
+        uint32_t cnt_n = 0;            // CNT: in-loop rounds
         const int dr = TS_DET_THREADS / W4, dq = TS_DET_THREADS - dr * W4;
         int yy = (wave * 64 + lane) / W4, q = wave * 64 + lane - yy * W4;   // stepped without a division
         for (int i0 = wave * 64; i0 < (yhi - ylo) * W4;
@@ -798,11 +824,22 @@ __device__ __forceinline__ void detect_body(const BatchCtx& c, int bx, int img) 
                         (uint16_t)(((uint32_t)r << 9) | (uint32_t)q);
             nn += (int)__popcll(bm);
             if (nn >= 64) {
-                nms_flush(nq + nn - 64, 64, sc32, W4, W, M, y0, cand, &s_count, s_hist);
                 nn -= 64;
+                nms_flush(nq[nn + lane], true, sc32, W4, W, M, y0, cand, &s_count, s_hist);
+                if (CNT) ++cnt_n;
             }
         }
-        if (nn > 0) nms_flush(nq, nn, sc32, W4, W, M, y0, cand, &s_count, s_hist);
+        // the wave's own tail: pooling the NMS tails over the block as phase B does halved their
+        // rounds (132 -> 68 per image) but not the kernel's time (measured)
+        if (nn > 0) nms_flush(nq[lane], lane < nn, sc32, W4, W, M, y0, cand, &s_count, s_hist);
+        if (CNT && lane == 0) {
+            uint32_t* dc = c.det_cnt + l * TS_DCNT;
+            if (cnt_n) atomicAdd(&dc[6], cnt_n);
+            if (nn > 0) {
+                atomicAdd(&dc[7], 1u);
+                atomicAdd(&dc[8], (uint32_t)nn);
+            }
+        }
     } else {
         const int xspan = W - 2 * M, nchx = (xspan + 63) >> 6;
         for (int it = wave; it < (yhi - ylo) * nchx; it += TS_DET_WAVES) {
@@ -835,7 +872,10 @@ __device__ __forceinline__ void detect_body(const BatchCtx& c, int bx, int img) 
 // 6 waves per SIMD (VGPRs <= 80; 71 without spills at TS_DET_U = 2): three 512-thread blocks per CU, as the LDS
 // allows, instead of two at 84 VGPRs (567 -> 528 us per 256-frame batch alone)
 __global__ __launch_bounds__(TS_DET_THREADS) __attribute__((amdgpu_waves_per_eu(6))) void k_detect(BatchCtx c) {
-    detect_body<0>(c, blockIdx.x, blockIdx.y);
+    detect_body<0, false>(c, blockIdx.x, blockIdx.y);
+}
+__global__ __launch_bounds__(TS_DET_THREADS) __attribute__((amdgpu_waves_per_eu(6))) void k_detect_counted(BatchCtx c) {
+    detect_body<0, true>(c, blockIdx.x, blockIdx.y);
 }
 
 // The exact fallback at t + 1 for the image-levels whose speculative select came short (rare):
@@ -867,14 +907,17 @@ __device__ __forceinline__ void for_flagged_levels(const BatchCtx& c, int nthrea
     }
 }
 
-__global__ __launch_bounds__(TS_DET_THREADS) void k_detect_fallback(BatchCtx c) {
+template <bool CNT>
+__device__ __forceinline__ void detect_fallback_body(const BatchCtx& c) {
     for_flagged_levels(c, TS_DET_THREADS, [&](int img, int l) {
         for (int b = 0; b < c.g.nbands[l]; ++b) {
-            detect_body<1>(c, c.g.band_start[l] + b, img);
+            detect_body<1, CNT>(c, c.g.band_start[l] + b, img);
             __syncthreads();
         }
     });
 }
+__global__ __launch_bounds__(TS_DET_THREADS) void k_detect_fallback(BatchCtx c) { detect_fallback_body<false>(c); }
+__global__ __launch_bounds__(TS_DET_THREADS) void k_detect_fallback_counted(BatchCtx c) { detect_fallback_body<true>(c); }
 
 // ---------------------------------------------------------------------------------------------
 // A4 top-K: exact K_l smallest keys of an image level, sorted ascending.
@@ -1311,7 +1354,7 @@ void launch_detect(const BatchCtx& c, hipStream_t s) {
     dim3 grid(c.g.total_bands, c.n * c.ncam);
     // hist [B][C][L][256] is zero here: zeroed at allocation, and every select (speculative or
     // fallback) zeroes its image-level's histogram once it has read it
-    hipLaunchKernelGGL(k_detect, grid, dim3(TS_DET_THREADS), lds, s, c);
+    hipLaunchKernelGGL(c.det_cnt ? k_detect_counted : k_detect, grid, dim3(TS_DET_THREADS), lds, s, c);
 }
 
 // next batch's te <- this batch's running minimum; the minimum restarts (view cameras)
@@ -1354,7 +1397,8 @@ void launch_select(const BatchCtx& c, hipStream_t s, int mode, int rcap) {
     launch_select_shape<SelWave>(c, s, mode, rcap, shape_of, 0);
     // fallback for images whose speculative threshold left fewer than K candidates: detect and
     // select again at t + 1, gated on the device flags (near-empty launches when none is set)
-    hipLaunchKernelGGL(k_detect_fallback, dim3(TS_FB_BLOCKS), dim3(TS_DET_THREADS), (size_t)c.g.det_lds, s, c);
+    hipLaunchKernelGGL(c.det_cnt ? k_detect_fallback_counted : k_detect_fallback, dim3(TS_FB_BLOCKS), dim3(TS_DET_THREADS),
+                       (size_t)c.g.det_lds, s, c);
     hipLaunchKernelGGL(k_select_fallback, dim3(TS_FB_BLOCKS), dim3(SEL_THREADS), 0, s, c);
     hipLaunchKernelGGL(k_det_thr_commit, dim3(1), dim3(256), 0, s, c);
 }

@@ -218,6 +218,7 @@ BatchCtx make_ctx(tslam_handle* h) {
     c.mp.refine_split = h->prm.match_refine;
     c.mp.merge_cap = h->match_mode == 1 ? 0 : h->match_cap > 0 ? std::min(h->match_cap, TS_MTB) : TS_MTB;
     c.match_cnt = h->d_match_cnt;
+    c.det_cnt = h->d_det_cnt;
     c.pp.n_hyp = h->prm.ransac_hypotheses;
     c.pp.iters = h->prm.refine_iters;
     c.pp.min_inliers = h->prm.min_inliers;
@@ -897,6 +898,22 @@ int tslam_match_counters(tslam_handle* h, uint32_t* counters16, int* blocks_per_
     HIPCHK(hipMemset(h->d_match_cnt, 0, sizeof(uint32_t) * 16));
     HIPCHK(hipDeviceSynchronize());
     if (blocks_per_cu) *blocks_per_cu = match_blocks_per_cu();
+    return TSLAM_OK;
+}
+
+int tslam_detect_counters(tslam_handle* h, uint32_t* counters, int max_levels) {
+    if (!h || max_levels < 0) return fail(TSLAM_EINVAL, "bad handle or level count");
+    int rc = tslam_sync(h);
+    if (rc != TSLAM_OK) return rc;
+    const size_t bytes = sizeof(uint32_t) * TS_MAX_LEVELS * TS_DCNT;
+    if (!h->d_det_cnt) {
+        if ((rc = dev_alloc(h, (void**)&h->d_det_cnt, bytes)) != TSLAM_OK) return rc;
+    }
+    const int nl = std::min(max_levels, (int)TS_MAX_LEVELS);
+    if (counters && nl > 0)
+        HIPCHK(hipMemcpy(counters, h->d_det_cnt, sizeof(uint32_t) * TS_DCNT * (size_t)nl, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemset(h->d_det_cnt, 0, bytes));
+    HIPCHK(hipDeviceSynchronize());
     return TSLAM_OK;
 }
 

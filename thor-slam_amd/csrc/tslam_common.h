@@ -29,6 +29,11 @@
 #include <stdint.h>
 
 #define TS_MAX_LEVELS 6
+// tslam_detect_counters: per level, three stages (phase B bright, phase B dark, NMS) x (rounds of 64
+// inside the loop, tail rounds, lanes filled in the tail rounds), then the blocks that ran.  Phase
+// B's tails are pooled over the block's waves; an NMS tail round is a wave's own.
+#define TS_DCNT 12
+#define TS_DCNT_BLOCKS 9
 // detect band height: 32 rows while the band's LDS (2 * rows + 10 rows of W bytes) stays <= 48 KiB
 // (3 blocks per CU; fewer halo rows and barriers per pixel), else 24 or 16 (LevelGeom::band_rows)
 #define TS_BAND_ROWS_MAX 32
@@ -167,6 +172,7 @@ struct BatchCtx {
     uint32_t* det_thr_acc;        // [C][L]
     uint32_t* det_fail;           // [B][C][L]
     uint32_t* match_cnt;          // [16] k_match path counters (tslam_match_counters) or null
+    uint32_t* det_cnt;            // [TS_MAX_LEVELS][TS_DCNT] k_detect round counters (tslam_detect_counters) or null
 
     const uint32_t* brief_table;  // [30][256] LDS patch byte offsets of the two points (lo | hi << 16)
     const int64_t* wedges;        // [31][2]

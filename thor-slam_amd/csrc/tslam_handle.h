@@ -122,6 +122,7 @@ struct tslam_handle {
     // the merge array's entries (0: TS_MTB), and the path counters tslam_match_counters switches on
     int match_mode = 0, match_cap = 0;
     uint32_t* d_match_cnt = nullptr;
+    uint32_t* d_det_cnt = nullptr;   // tslam_detect_counters switches the counted k_detect build on
     struct {
         bool pending = false;
         BatchCtx c{};

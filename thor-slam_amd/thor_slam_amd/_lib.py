@@ -36,6 +36,7 @@ INE_RECORD = 80   # TSLAM_BA_INE_RECORD: doubles of an inertial factor record
 RIG_KERNEL = 18   # rig pose (+ chain; sharded: the range's rig pose only)
 POSE_SOLVE_KERNEL = 19   # P3P + RANSAC + refine on injected correspondences (parity tests)
 TRANSPORT = {"rccl": 0, "copy": 1}   # tslam_group_create
+DET_COUNTERS, DET_COUNTER_BLOCKS = 12, 9   # tslam_detect_counters: words per level (TS_DCNT), index of the block count
 SHARD_GATHER, SHARD_RESULTS, SHARD_PROFILE, SHARD_SERIAL, SHARD_PIPELINE, SHARD_SOLO, SHARD_PAIRS = 1, 2, 4, 8, 16, 32, 64   # tslam_shard_options
 # tslam_shard_timing segments (enum tslam_segment), in order
 SHARD_SEGMENTS = ("rectify_pyramid", "detect", "select", "describe", "pack", "exchange_wait", "import", "match",
@@ -275,6 +276,7 @@ _SIGNATURES = {
     "tslam_select_mode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
     "tslam_match_mode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
     "tslam_match_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int)]),
+    "tslam_detect_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int]),
     "tslam_ba_inertial": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
                                          ctypes.c_void_p, ctypes.c_double]),
     "tslam_ba_inertial_factor": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p,
@@ -1424,6 +1426,22 @@ class Handle:
         names = ("merged", "direct", "flushed", "empty_blocks", "walked_blocks")
         out = {m: {k: int(cnt[8 * i + j]) for j, k in enumerate(names)} for i, m in enumerate(("stereo", "temporal"))}
         out["blocks_per_cu"] = bpc.value
+        return out
+
+    def detect_counters(self) -> list:
+        """``tslam_detect_counters``: the detector's flush rounds since the last call (the first call
+        switches counting on).  Per level a dict: for ``bright`` / ``dark`` (phase B) the ``inloop``
+        rounds, the ``pooled`` tail rounds and the ``lanes`` filled in them; for ``nms`` the ``inloop``
+        rounds, the waves' own ``partial`` tail rounds and their ``lanes``; and the ``blocks`` run."""
+        L = self.cfg.n_levels
+        cnt = (ctypes.c_uint32 * (DET_COUNTERS * L))()
+        _check(self.lib.tslam_detect_counters(self.h, cnt, L))
+        out = []
+        for l in range(L):
+            lev = {s: {k: int(cnt[DET_COUNTERS * l + 3 * i + j]) for j, k in enumerate(("inloop", "partial" if s == "nms" else "pooled", "lanes"))}
+                   for i, s in enumerate(("bright", "dark", "nms"))}
+            lev["blocks"] = int(cnt[DET_COUNTERS * l + DET_COUNTER_BLOCKS])
+            out.append(lev)
         return out
 
     def ba_graph(self, enable: bool) -> None:
