@@ -87,6 +87,21 @@ constexpr DiscTable make_disc_table() {
 }
 __constant__ DiscTable c_disc = make_disc_table();
 
+// Per-lane wedge directions of the orientation bins as doubles: lane b < 30 tests bin b against the
+// directions b and b + 1 of the table the host ships to the device (tslam_tables.h); lanes 30.. hold
+// zeros and never hit.  Built at compile time like c_disc: two 16-byte loads per lane.
+#include "tslam_tables.h"
+struct WedgeTable {
+    double e[64][4];
+};
+constexpr WedgeTable make_wedge_table() {
+    WedgeTable t{};
+    for (int b = 0; b < 30; ++b)
+        for (int j = 0; j < 4; ++j) t.e[b][j] = (double)TSLAM_WEDGES[2 * b + j];
+    return t;
+}
+__constant__ WedgeTable c_wedge = make_wedge_table();
+
 __global__ __launch_bounds__(TS_DT_THREADS) void k_describe(BatchCtx c) {
     // raw tile: the orientation discs' columns [x0 - 16, x0 + 144) only (10 chunks), + 1 row of
     // slack for the masked bytes the last disc row's dword window reads past the row end
@@ -95,49 +110,60 @@ __global__ __launch_bounds__(TS_DT_THREADS) void k_describe(BatchCtx c) {
     __shared__ uint16_t s_list[TS_DT_W * TS_DT_H / 4];   // NMS keeps at most one per 2x2
     __shared__ uint32_t s_n;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // block -> (image, level, tile); all tiles of one image on one XCD (tile geometry from the
-    // host: no scalar divisions per block beyond the tile's row)
+    // block -> (image, level, tile) from the grid (8, dt_total, image groups) and the host's tile
+    // table: all tiles of one image on one XCD, no division and no level search
     int img, local;
-    if (!xcd_image_block(blockIdx.x, c.n * c.ncam, c.g.dt_total, &img, &local)) return;
-    int l = 0;
-    while (l + 1 < c.g.n_levels && local >= c.g.dt_start[l + 1]) ++l;
-    local -= c.g.dt_start[l];
-    const int nx = c.g.dt_nx[l];
-    const int ty = local / nx, tx = local - ty * nx;
+    if (!xcd_image_block3(c.n * c.ncam, c.g.dt_total, &img, &local)) return;
+    const uint32_t tile = c.dt_tile[local];
+    const int l = (int)(tile & 0xFFu), tx = (int)((tile >> 8) & 0xFFu), ty = (int)(tile >> 16);
+    const bool first = local == c.g.dt_start[l];   // the level's first tile
     const int W = c.g.W[l], H = c.g.H[l];
     const int x0 = tx * TS_DT_W, y0 = ty * TS_DT_H;
     int cam, f;
     view_image(c, img, &f, &cam);
-    const int slot = ring_slot(c, c.g0 + f);
+    const int slot = batch_slot(c, f);
     const size_t ib = (size_t)slot * c.C + cam;
+    const int koff = c.g.koff[l];
     const uint8_t* raw = c.pyr + ib * c.g.pyr_bytes + c.g.pyr_off[l];
     const uint8_t* smo = c.smo + ((size_t)f * c.C + cam) * c.g.pyr_bytes + c.g.pyr_off[l];
     uint32_t* kps = c.kps + ib * c.g.K * 2;
     uint32_t* desc = c.desc + ib * c.g.K * 8;
-    uint32_t* desc_ys = c.desc_ys + ib * c.g.K * 8;
-    const uint4* ys = c.ys + ib * c.g.K + c.g.koff[l];
-    const uint16_t* rs = c.rowstart + ib * c.g.rs_total + c.g.rs_off[l];
-    const int kn = c.kcount[ib * c.g.n_levels + l];
-
-    // padding slots of the level get zero descriptors (first tile of the level does it)
-    if (local == 0) {
-        const int Kl = c.g.Kq[l];
-        for (int i = kn * 8 + threadIdx.x; i < Kl * 8; i += TS_DT_THREADS) {
-            desc[(size_t)(c.g.koff[l] + i / 8) * 8 + (i & 7)] = 0u;
-            desc_ys[(size_t)(c.g.koff[l] + i / 8) * 8 + (i & 7)] = 0u;
-        }
-    }
-    const int pa = rs[y0], pb = rs[min(y0 + TS_DT_H, H)];
-    if (pa >= pb) return;   // no keypoint in the tile's rows (block-uniform)
+    uint32_t* desc_ys = c.desc_ys + (ib * c.g.K + koff) * 8;   // the level's y-sorted descriptors
+    const uint4* ys = c.ys + ib * c.g.K + koff;
+    // the tile's range of y-sorted records: two u16 of the row-start table, each read as its
+    // aligned dword (the image's table starts on 16 bytes) so that the uniform loads can take the
+    // scalar path and are not waited for together with the tile copies below
+    const size_t ra = ib * c.g.rs_total + c.g.rs_off[l] + y0, rb = ra + (min(y0 + TS_DT_H, H) - y0);
+    const uint32_t* rs32 = reinterpret_cast<const uint32_t*>(c.rowstart);
+    const uint32_t wa = rs32[ra >> 1], wb = rs32[rb >> 1];
+    const int kn = first ? c.kcount[ib * c.g.n_levels + l] : 0;
     if (threadIdx.x == 0) s_n = 0;
-    __syncthreads();
+    __syncthreads();   // before any copy is in flight: a barrier waits for the block's loads
 
+    // both tiles on their way before anything is waited for: the list, the constants and the
+    // level's padding run while the LDS-DMA is in flight
     const bool wide16 = ((W & 15) == 0) && ((c.g.pyr_off[l] & 15) == 0) && ((c.g.pyr_bytes & 15) == 0);
     const int c0 = x0 - TS_DT_HX;        // smoothed tile's column origin (pitch TS_DT_P)
     const int cr = x0 - 16;              // raw tile's column origin (pitch TS_DT_RAW_P)
     stage_tile<TS_DT_RAW_P / 16>(raw, W, H, y0 - 15, cr, TS_DT_RAW_ROWS, s_raw, wide16);
     // smoothed tile: BRIEF reads columns [x0 - 18, x0 + 146): chunks 0..11; chunk 12 is the pad
     stage_tile<TS_DT_P / 16, (TS_DT_W + 2 * TS_DT_HX) / 16>(smo, W, H, y0 - 18, c0, TS_DT_SMO_ROWS, s_smo, wide16);
+
+    // padding slots of the level get zero descriptors (first tile of the level does it)
+    if (first) {
+        const int Kl = c.g.Kq[l];
+        for (int i = kn * 8 + threadIdx.x; i < Kl * 8; i += TS_DT_THREADS) {
+            desc[(size_t)(koff + i / 8) * 8 + (i & 7)] = 0u;
+            desc_ys[i] = 0u;
+        }
+    }
+    const int pa = (int)((wa >> (16 * (ra & 1))) & 0xFFFFu), pb = (int)((wb >> (16 * (rb & 1))) & 0xFFFFu);
+    if (pa >= pb) {
+        // no keypoint in the tile's rows (block-uniform): the copies must land before the block
+        // ends, or they would land in LDS that the next block already owns
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        return;
+    }
 
     // per-lane disc constants (slot s = lane + 64 i; see DiscTable)
     uint32_t wx[5], mk[5], wy[5];
@@ -152,8 +178,7 @@ __global__ __launch_bounds__(TS_DT_THREADS) void k_describe(BatchCtx c) {
     }
     // wedge directions as doubles: |u| < 2^25 and |m| < 2^23, so every product and difference
     // below is an exact integer in f64 (< 2^53) and the sign tests equal the int64 ones
-    const double wa0 = lane < 30 ? (double)c.wedges[2 * lane] : 0.0, wa1 = lane < 30 ? (double)c.wedges[2 * lane + 1] : 0.0;
-    const double wb0 = lane < 30 ? (double)c.wedges[2 * lane + 2] : 0.0, wb1 = lane < 30 ? (double)c.wedges[2 * lane + 3] : 0.0;
+    const double wa0 = c_wedge.e[lane][0], wa1 = c_wedge.e[lane][1], wb0 = c_wedge.e[lane][2], wb1 = c_wedge.e[lane][3];
 
     // keypoints of the tile: the records of its rows filtered by x, compacted into an LDS list
     // so the 4 waves get equal shares (order is irrelevant: every keypoint is independent)
@@ -179,7 +204,7 @@ __global__ __launch_bounds__(TS_DT_THREADS) void k_describe(BatchCtx c) {
             if (pos[g] < 0) continue;
             const int x = rec[g].x & 0xFFFF, y = rec[g].x >> 16;
             // orientation: disc origin (x - 15, y - 15) in the raw tile
-            const int ob = (y - y0) * TS_DT_RAW_P + (x - 15 - cr);
+            const int ob = (int)__umul24((uint32_t)(y - y0), TS_DT_RAW_P) + (x - 15 - cr);   // both < 2^24
             const uint32_t sh = (uint32_t)ob & 3u;
             const uint8_t* obase = s_raw + (ob & ~3);
             uint32_t sx = 0, s1 = 0, sy = 0;
@@ -210,7 +235,7 @@ __global__ __launch_bounds__(TS_DT_THREADS) void k_describe(BatchCtx c) {
             if (pos[g] < 0) continue;
             const int x = rec[g].x & 0xFFFF, y = rec[g].x >> 16;
             // BRIEF: patch origin (x - 18, y - 18) in the smoothed tile
-            const uint8_t* pbase = s_smo + (y - y0) * TS_DT_P + (x - 18 - c0);
+            const uint8_t* pbase = s_smo + ((int)__umul24((uint32_t)(y - y0), TS_DT_P) + (x - 18 - c0));
             uint32_t words[8];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -227,7 +252,7 @@ __global__ __launch_bounds__(TS_DT_THREADS) void k_describe(BatchCtx c) {
             for (int j = 0; j < 8; ++j) asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(w) : "s"(words[j]), "i"(j));
             if (lane < 8) {
                 desc[(size_t)kidx * 8 + lane] = w;
-                desc_ys[(size_t)(c.g.koff[l] + pos[g]) * 8 + lane] = w;
+                desc_ys[(size_t)pos[g] * 8 + lane] = w;
             }
             if (lane == 0) kps[(size_t)kidx * 2 + 1] = (rec[g].y & ~0xFF00u) | ((uint32_t)bin[g] << 8);
         }
@@ -235,5 +260,5 @@ __global__ __launch_bounds__(TS_DT_THREADS) void k_describe(BatchCtx c) {
 }
 
 void launch_describe(const BatchCtx& c, hipStream_t s) {
-    hipLaunchKernelGGL(k_describe, dim3(xcd_grid(c.n * c.ncam, c.g.dt_total)), dim3(TS_DT_THREADS), 0, s, c);
+    hipLaunchKernelGGL(k_describe, xcd_grid3(c.n * c.ncam, c.g.dt_total), dim3(TS_DT_THREADS), 0, s, c);
 }

@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void k_rectify_pyramid(BatchCtx c) {
     const int y0 = blockIdx.x * TS_RECT_BAND;
     const int rows0 = min(TS_RECT_BAND, H - y0);
     const uint8_t* src = c.images + view_src(c, img) * W * H;
-    uint8_t* pyr = c.pyr + ((size_t)ring_slot(c, c.g0 + f) * c.C + cam) * c.g.pyr_bytes;
+    uint8_t* pyr = c.pyr + ((size_t)batch_slot(c, f) * c.C + cam) * c.g.pyr_bytes;
     const bool has_map = (c.map_mask >> cam) & 1u;
     const int32_t* map = c.maps + (size_t)cam * W * H * 2;
     // 16-byte rows everywhere (W % 64 == 0 keeps every level's rows 16-byte aligned for 4 levels;
@@ -567,7 +567,7 @@ __device__ __forceinline__ void detect_body(const BatchCtx& c, int bx, int img) 
     const int BR = c.g.band_rows[l];
     const int y0 = band * BR;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const size_t img_off = ((size_t)ring_slot(c, c.g0 + f) * c.C + cam) * c.g.pyr_bytes + c.g.pyr_off[l];
+    const size_t img_off = ((size_t)batch_slot(c, f) * c.C + cam) * c.g.pyr_bytes + c.g.pyr_off[l];
     const uint8_t* src = c.pyr + img_off;
     uint8_t* smo = c.smo + ((size_t)f * c.C + cam) * c.g.pyr_bytes + c.g.pyr_off[l];
     const int NR = BR + 2 * TS_DET_HALO;
@@ -1200,7 +1200,7 @@ __device__ __forceinline__ void select_body(const BatchCtx& c, int img, int l, i
     });
     __syncthreads();
     const int nsel = min((int)s_nsel, Kl);
-    const int slot = ring_slot(c, c.g0 + f);
+    const int slot = batch_slot(c, f);
     uint32_t* kp = c.kps + (((size_t)slot * c.C + cam) * c.g.K + c.g.koff[l]) * 2;
     const int Hl = c.g.H[l];
     // Counting sorts (few barriers) when the level fits s_tmp (always, unless the shape is BIG)

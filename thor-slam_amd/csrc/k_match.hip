@@ -102,8 +102,8 @@ __device__ __forceinline__ void match_body(const BatchCtx& c) {
     const int z = blockIdx.y;
     const int mode = z < nfp ? 1 : 0;
     const int fl = z < nfp ? z : z - nfp;     // f * npair + (p - pair0)
-    const int p = c.pair0 + fl % c.npair;
-    const int f = fl / c.npair;
+    const int f = div_small(fl, c.npair_rcp);
+    const int p = c.pair0 + (fl - f * c.npair);
     const int64_t g = c.g0 + f;
     int l = 0;
     while (l + 1 < c.g.n_levels && (int)blockIdx.x >= c.g.qtile_start[l + 1]) ++l;
@@ -121,9 +121,9 @@ __device__ __forceinline__ void match_body(const BatchCtx& c) {
         no_match();
         return;
     }
-    const int slot = ring_slot(c, g);
+    const int slot = batch_slot(c, f);
     const int qcam = c.cpp * p;
-    const int tslot = mode == 0 ? slot : ring_slot(c, g - 1);
+    const int tslot = mode == 0 ? slot : prev_slot(c, slot);
     const int tcam = mode == 0 ? qcam + 1 : qcam;
     const int K = c.g.K;
     const int qn = c.kcount[((size_t)slot * c.C + qcam) * c.g.n_levels + l];
@@ -479,7 +479,10 @@ __device__ __forceinline__ uint4 stage_row11(const uint8_t* img, int W, int y, i
     return uint4{w3[0], w3[1], w3[2], 0u};
 }
 
-// ... or the 15 window bytes (byte 15 zero): 5 aligned dwords `d` + v_alignbyte by the address's low bits
+// ... or the 15 window bytes (byte 15 zero): 5 aligned dwords `d` + v_alignbyte by the address's low bits.
+// A row that starts in byte 0 or 1 of its first dword ends inside the fourth: its lane skips the fifth load
+// (the refinement is bound by its address path; one unaligned 16-byte load per row instead was as fast
+// alone and 0.07 ms slower in the pipelined C2 step)
 __device__ __forceinline__ uint4 align_row15(const uint32_t* d, uint32_t sh) {
     return uint4{__builtin_amdgcn_alignbyte(d[1], d[0], sh), __builtin_amdgcn_alignbyte(d[2], d[1], sh),
                  __builtin_amdgcn_alignbyte(d[3], d[2], sh), __builtin_amdgcn_alignbyte(d[4], d[3], sh) & 0x00FFFFFFu};
@@ -488,7 +491,7 @@ __device__ __forceinline__ uint4 stage_row15(const uint8_t* img, int W, int y, i
     const uint8_t* a = img + (size_t)y * W + x0;
     const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3u);
     const uint32_t* q = reinterpret_cast<const uint32_t*>(a - sh);
-    const uint32_t d[5] = {q[0], q[1], q[2], q[3], q[4]};
+    const uint32_t d[5] = {q[0], q[1], q[2], q[3], sh >= 2u ? q[4] : 0u};
     return align_row15(d, sh);
 }
 
@@ -631,7 +634,7 @@ __device__ __forceinline__ int match_lookup(const BatchCtx& c, size_t mbase, int
 // 22 rows dealt over the 8 lanes, so a query costs ~27 row loads instead of 5 x 88 scattered
 // dword gathers (the texture-address path, not the VALU, bound the per-lane version); sub-lanes
 // 0..4 score the 5 offsets from LDS; the first minimum is an xor-shuffle over the 8 lanes.
-// grid xcd_grid(n*P, ceil(K/32)), block 256.
+// grid xcd_grid3(n*P, ceil(K/32)), block 256.
 #define TS_RS_QPB 32   // queries per block
 __global__ __launch_bounds__(256) void k_refine_stereo(BatchCtx c) {
     TS_BACK_PRIO;
@@ -641,10 +644,9 @@ __global__ __launch_bounds__(256) void k_refine_stereo(BatchCtx c) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int K = c.g.K;
     int z, local;
-    if (!xcd_image_block(blockIdx.x, c.n * c.npair, (K + TS_RS_QPB - 1) / TS_RS_QPB, &z, &local)) return;
-    const int p = c.pair0 + z % c.npair, f = z / c.npair;
-    const int64_t g = c.g0 + f;
-    const int slot = ring_slot(c, g);
+    if (!xcd_image_block3(c.n * c.npair, (K + TS_RS_QPB - 1) / TS_RS_QPB, &z, &local)) return;
+    const int f = div_small(z, c.npair_rcp), p = c.pair0 + (z - f * c.npair);
+    const int slot = batch_slot(c, f);
     const int sub = lane & 7;
     const int qslot = wave * 8 + (lane >> 3);
     const int pos = local * TS_RS_QPB + qslot;
@@ -695,7 +697,7 @@ __global__ __launch_bounds__(256) void k_refine_stereo(BatchCtx c) {
 // query's 11x11 patch at t-1 and its 15x15 search window at t are staged in LDS (sub-lane s loads
 // rows s, s+8, .. of the 26), rows padded to 16 bytes and read back as ds_read_b128; sub-lane s
 // scores offsets s, s+8, s+16, s+24 of the 25; the first minimum is an xor-shuffle over the 8
-// lanes.  grid xcd_grid(n*P, ceil(K/32)), block 256.
+// lanes.  grid xcd_grid3(n*P, ceil(K/32)), block 256.
 #define TS_RT_QPB 32   // queries per block
 __global__ __launch_bounds__(256) void k_refine_temporal(BatchCtx c) {
     TS_BACK_PRIO;
@@ -705,10 +707,10 @@ __global__ __launch_bounds__(256) void k_refine_temporal(BatchCtx c) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int K = c.g.K;
     int z, local;
-    if (!xcd_image_block(blockIdx.x, c.n * c.npair, (K + TS_RT_QPB - 1) / TS_RT_QPB, &z, &local)) return;
-    const int p = c.pair0 + z % c.npair, f = z / c.npair;
-    const int64_t g = c.g0 + f;
-    const int slot = ring_slot(c, g);
+    if (!xcd_image_block3(c.n * c.npair, (K + TS_RT_QPB - 1) / TS_RT_QPB, &z, &local)) return;
+    const int f = div_small(z, c.npair_rcp), p = c.pair0 + (z - f * c.npair);
+    const bool has_prev = c.g0 + f > 0;   // frame 0 of the sequence: nothing matches
+    const int slot = batch_slot(c, f);
     const int sub = lane & 7;
     const int qslot = wave * 8 + (lane >> 3);
     const int pos = local * TS_RT_QPB + qslot;
@@ -718,13 +720,13 @@ __global__ __launch_bounds__(256) void k_refine_temporal(BatchCtx c) {
     const size_t qkb = ((size_t)slot * c.C + qcam) * K;
     int l = 0, qi = 0, j = -1;
     uint32_t qxy = 0, pxy = 0;
-    const int pslot = g > 0 ? ring_slot(c, g - 1) : slot;   // frame 0: nothing matches
+    const int pslot = has_prev ? prev_slot(c, slot) : slot;
     if (live) {
         const uint4 rec = c.ys[qkb + pos];
         qi = (int)rec.z;
         l = (int)(rec.y & 0xFFu);
         qxy = rec.x;
-        j = match_lookup(c, mbase, pos, qi, rec.w != 0 && g > 0, ((size_t)pslot * c.C + qcam) * K, &pxy);
+        j = match_lookup(c, mbase, pos, qi, rec.w != 0 && has_prev, ((size_t)pslot * c.C + qcam) * K, &pxy);
     }
     int32_t* out_idx = c.temporal + ((size_t)slot * c.P + p) * K;
     double* out_uv = c.tuv + (((size_t)f * c.P + p) * K + qi) * 2;
@@ -772,7 +774,7 @@ __global__ __launch_bounds__(256) void k_refine_temporal(BatchCtx c) {
 // bytes 2..12 of the temporal kernel's 15x15 window.  Here a query loads its record and both
 // modes' (qbest, qsecond) in one round and both trains' (tbest, keypoint word) in the next, then
 // stages each image region once, its rows dealt over the 8 sub-lanes with every round's loads in
-// flight together (one instruction stream: any row is 15 bytes from 5 aligned dwords; the t-1
+// flight together (one instruction stream: any row is 15 bytes from 4 or 5 aligned dwords; the t-1
 // patch rows are cut to 11):
 //   rows  0..14  the window at t (temporal match), or its rows 2..12 only (stereo match alone)
 //   rows 15..25  the 11x11 patch at t-1            (temporal match)
@@ -792,11 +794,11 @@ __global__ __launch_bounds__(256) void k_refine_pair(BatchCtx c) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int K = c.g.K;
     int z, local;
-    if (!xcd_image_block(blockIdx.x, c.n * c.npair, (K + TS_RP_QPB - 1) / TS_RP_QPB, &z, &local)) return;
-    const int p = c.pair0 + z % c.npair, f = z / c.npair;
-    const int64_t g = c.g0 + f;
-    const int slot = ring_slot(c, g);
-    const int pslot = g > 0 ? ring_slot(c, g - 1) : slot;   // frame 0: nothing matches
+    if (!xcd_image_block3(c.n * c.npair, (K + TS_RP_QPB - 1) / TS_RP_QPB, &z, &local)) return;
+    const int f = div_small(z, c.npair_rcp), p = c.pair0 + (z - f * c.npair);
+    const bool has_prev = c.g0 + f > 0;   // frame 0 of the sequence: nothing matches
+    const int slot = batch_slot(c, f);
+    const int pslot = has_prev ? prev_slot(c, slot) : slot;
     const int sub = lane & 7;
     const int qslot = wave * 8 + (lane >> 3);
     const int pos = local * TS_RP_QPB + qslot;
@@ -817,7 +819,7 @@ __global__ __launch_bounds__(256) void k_refine_pair(BatchCtx c) {
         match_train(c, mbase, ((size_t)slot * c.C + qcam + 1) * K, &ms, &tkp);
         match_train(c, mbase + K, ((size_t)pslot * c.C + qcam) * K, &mt, &pxy);
         js = match_accept(c, ms, qi, rec.w != 0);
-        jt = match_accept(c, mt, qi, rec.w != 0 && g > 0);
+        jt = match_accept(c, mt, qi, rec.w != 0 && has_prev);
     }
     const size_t out = ((size_t)slot * c.P + p) * K + qi;
     if (live && sub == 0) c.temporal[out] = jt;
@@ -851,7 +853,9 @@ __global__ __launch_bounds__(256) void k_refine_pair(BatchCtx c) {
             sh[k] = (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3u);
             const uint32_t* q = reinterpret_cast<const uint32_t*>(a - sh[k]);
 #pragma unroll
-            for (int i = 0; i < 5; ++i) d[k][i] = q[i];
+            for (int i = 0; i < 4; ++i) d[k][i] = q[i];
+            // the fifth dword only where a 15-byte row reaches into it (the t - 1 patch rows are 11 bytes)
+            d[k][4] = (!inp && sh[k] >= 2u) ? q[4] : 0u;
         }
 #pragma unroll
         for (int k = 0; k < TS_RP_ROUNDS; ++k) {
@@ -923,19 +927,19 @@ void launch_match_stereo(const BatchCtx& c, hipStream_t s) {
     st.match_modes = 1;
     (void)hipMemsetAsync(st.tbest, 0xFF, sizeof(uint32_t) * (size_t)st.n * st.P * 2 * st.g.K, s);
     launch_k_match(st, dim3(st.g.total_qtiles, st.n * st.npair), s);
-    hipLaunchKernelGGL(k_refine_stereo, dim3(xcd_grid(st.n * st.npair, (st.g.K + TS_RS_QPB - 1) / TS_RS_QPB)), dim3(256), 0, s, st);
+    hipLaunchKernelGGL(k_refine_stereo, xcd_grid3(st.n * st.npair, (st.g.K + TS_RS_QPB - 1) / TS_RS_QPB), dim3(256), 0, s, st);
 }
 
 void launch_match_refine(const BatchCtx& c, hipStream_t s) {
     const int K = c.g.K;
     // a stereo frame's two refinements in one kernel, unless tslam_params.match_refine asks for the two
     if (!c.rgbd && c.match_modes == 3 && c.mp.refine_split == 0) {
-        hipLaunchKernelGGL(k_refine_pair, dim3(xcd_grid(c.n * c.npair, (K + TS_RP_QPB - 1) / TS_RP_QPB)), dim3(256), 0, s, c);
+        hipLaunchKernelGGL(k_refine_pair, xcd_grid3(c.n * c.npair, (K + TS_RP_QPB - 1) / TS_RP_QPB), dim3(256), 0, s, c);
         return;
     }
     if (c.rgbd)
         launch_rgbd_depth(c, s);
     else
-        hipLaunchKernelGGL(k_refine_stereo, dim3(xcd_grid(c.n * c.npair, (K + TS_RS_QPB - 1) / TS_RS_QPB)), dim3(256), 0, s, c);
-    hipLaunchKernelGGL(k_refine_temporal, dim3(xcd_grid(c.n * c.npair, (K + TS_RT_QPB - 1) / TS_RT_QPB)), dim3(256), 0, s, c);
+        hipLaunchKernelGGL(k_refine_stereo, xcd_grid3(c.n * c.npair, (K + TS_RS_QPB - 1) / TS_RS_QPB), dim3(256), 0, s, c);
+    hipLaunchKernelGGL(k_refine_temporal, xcd_grid3(c.n * c.npair, (K + TS_RT_QPB - 1) / TS_RT_QPB), dim3(256), 0, s, c);
 }

@@ -260,8 +260,8 @@ __device__ __forceinline__ void write_stats(int32_t* so, int status, int n, int 
 __global__ __launch_bounds__(POSE_THREADS) void k_corr(BatchCtx c) {
     TS_BACK_PRIO;
     __shared__ int s_scan[2 * (POSE_THREADS / 64)];
-    const int p = c.pair0 + (int)blockIdx.x % c.npair;   // (frame, pair) of the pair view
-    const int f = (int)blockIdx.x / c.npair;
+    const int f = div_small((int)blockIdx.x, c.npair_rcp);   // (frame, pair) of the pair view
+    const int p = c.pair0 + ((int)blockIdx.x - f * c.npair);
     const int fp = f * c.P + p;
     const int64_t g = c.g0 + f;
     const int tid = threadIdx.x;
@@ -275,8 +275,8 @@ __global__ __launch_bounds__(POSE_THREADS) void k_corr(BatchCtx c) {
     }
     const PairCalib cal = c.calib[p];
     const double fx = cal.fx, fy = cal.fy, cx = cal.cx, cy = cal.cy;
-    const int pslot = ring_slot(c, g - 1);
-    const int32_t* tm = c.temporal + ((size_t)ring_slot(c, g) * c.P + p) * K;
+    const int slot = batch_slot(c, f), pslot = prev_slot(c, slot);
+    const int32_t* tm = c.temporal + ((size_t)slot * c.P + p) * K;
     const double* tuv = c.tuv + ((size_t)f * c.P + p) * K * 2;
     const double* dprev = c.disp + ((size_t)pslot * c.P + p) * K;
     const uint32_t* kprev = c.kps + ((size_t)pslot * c.C + c.cpp * p) * K * 2;

@@ -145,9 +145,8 @@ void launch_reloc_query(const BatchCtx& c, int pair, int64_t frame, RelocQuery q
     BatchCtx r = c;   // A7's RANSAC + refinement on the relocalisation scratch: one frame, one "pair"
     r.n = 1;
     r.P = 1;
-    r.pair0 = 0;
-    r.npair = 1;
-    r.g0 = frame;
+    ctx_set_views(r, r.cam0, r.ncam, 0, 1);
+    ctx_set_first_frame(r, frame);
     r.prior = nullptr;   // no IMU prior: the solve is the map's alone
     r.rig_prior = nullptr;
     r.calib[0] = c.calib[pair];
@@ -180,9 +179,8 @@ void launch_reloc_rig(const BatchCtx& c, int64_t frame, const double* map_xyz, c
     }
     BatchCtx r = c;   // one frame, every pair
     r.n = 1;
-    r.pair0 = 0;
-    r.npair = c.P;
-    r.g0 = frame;
+    ctx_set_views(r, r.cam0, r.ncam, 0, c.P);
+    ctx_set_first_frame(r, frame);
     r.corr = corr;
     r.stats = stats;
     r.pose = pose;

@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void k_rgbd_depth(BatchCtx c) {
     const int fl = blockIdx.y, p = c.pair0 + fl % c.npair, f = fl / c.npair;   // camera p = pair p
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= K) return;
-    const int slot = ring_slot(c, c.g0 + f);
+    const int slot = batch_slot(c, f);
     const size_t ib = (size_t)slot * c.C + p;
     const uint32_t* kp = c.kps + (ib * K + k) * 2;
     const int l = (int)(kp[1] & 0xFF);

@@ -161,7 +161,7 @@ BatchCtx make_ctx(tslam_handle* h) {
     c.B = h->B;
     c.R = h->R;
     c.n = h->cur_n;
-    c.g0 = h->cur_g0;
+    ctx_set_first_frame(c, h->cur_g0);
     c.W = h->W;
     c.H = h->H;
     c.cpp = h->prm.rgbd ? 1 : 2;
@@ -209,6 +209,7 @@ BatchCtx make_ctx(tslam_handle* h) {
     c.det_fail = (uint32_t*)h->buf[TSLAM_BUF_DET_FAIL].ptr;
     c.brief_table = h->d_brief;
     c.wedges = h->d_wedges;
+    c.dt_tile = h->d_dt_tile;
     for (int p = 0; p < h->P; ++p) c.calib[p] = h->calib[p];
     c.mp.max_hamming = h->prm.max_hamming;
     c.mp.ratio_pct = h->prm.ratio_pct;
@@ -229,10 +230,7 @@ BatchCtx make_ctx(tslam_handle* h) {
     c.pp.seed = h->prm.ransac_seed;
     c.fast_threshold = h->prm.fast_threshold;
     c.margin = h->prm.edge_margin;
-    c.cam0 = h->sh_cam_lo;
-    c.ncam = h->sh_cam_hi - h->sh_cam_lo;
-    c.pair0 = 0;
-    c.npair = h->P;
+    ctx_set_views(c, h->sh_cam_lo, h->sh_cam_hi - h->sh_cam_lo, 0, h->P);
     c.match_modes = 3;
     c.reloc = 0;
     c.peer_S = c.peer_me = c.peer_nbuf = c.peer_skip = 0;
@@ -410,6 +408,7 @@ int tslam_create(const tslam_stereo_desc* pairs, const tslam_params* params, int
     if (rc == TSLAM_OK) h->d_hyp = (double*)h->buf[TSLAM_BUF_HYP].ptr;
     if (rc == TSLAM_OK) rc = dev_alloc(h, (void**)&h->d_brief, sizeof(TSLAM_BRIEF_TABLE));
     if (rc == TSLAM_OK) rc = dev_alloc(h, (void**)&h->d_wedges, sizeof(TSLAM_WEDGES));
+    if (rc == TSLAM_OK) rc = dev_alloc(h, (void**)&h->d_dt_tile, sizeof(uint32_t) * (size_t)h->g.dt_total);
     if (rc == TSLAM_OK) rc = dev_alloc(h, (void**)&h->d_maps, sizeof(int32_t) * (size_t)C * W * H * 2);
     if (rc == TSLAM_OK && p.ba_window) rc = alloc_ba(h);
     if (rc == TSLAM_OK && p.rgbd) rc = dev_alloc(h, (void**)&h->d_gray, (size_t)B * P * W * H);
@@ -430,6 +429,9 @@ int tslam_create(const tslam_stereo_desc* pairs, const tslam_params* params, int
     }
     bool ok = hipMemcpy(h->d_brief, brief_off.data(), sizeof(uint32_t) * brief_off.size(), hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(h->d_wedges, TSLAM_WEDGES, sizeof(TSLAM_WEDGES), hipMemcpyHostToDevice) == hipSuccess;
+    std::vector<uint32_t> dt_tile(h->g.dt_total);
+    describe_tile_table(h->g, dt_tile.data());
+    ok = ok && hipMemcpy(h->d_dt_tile, dt_tile.data(), sizeof(uint32_t) * dt_tile.size(), hipMemcpyHostToDevice) == hipSuccess;
     for (int i = 0; i < h->P && ok; ++i) {
         const int32_t* m[2] = {pairs[i].map_left, pairs[i].map_right};
         const int cpp = p.rgbd ? 1 : 2;

@@ -9,7 +9,7 @@
 static BatchCtx range_ctx(const BatchCtx& c, int lo, int hi) {
     BatchCtx r = c;
     const size_t P = c.P, K = c.g.K, f = lo;
-    r.g0 = c.g0 + lo;
+    ctx_set_first_frame(r, c.g0 + lo);
     r.n = hi - lo;
     r.qbest += f * P * 2 * K;
     r.qsecond += f * P * 2 * K;
@@ -51,8 +51,7 @@ static int run_sharded_rgbd_stage(tslam_handle* h, const BatchCtx& c, int stage,
     int lo, hi;
     shard_range(h, c.n, &lo, &hi);
     BatchCtx own = c;   // pair view: this rank's cameras (cameras per pair = 1)
-    own.pair0 = h->sh_cam_lo;
-    own.npair = h->sh_cam_hi - h->sh_cam_lo;
+    ctx_set_views(own, own.cam0, own.ncam, h->sh_cam_lo, h->sh_cam_hi - h->sh_cam_lo);
     const BatchCtx cr = range_ctx(c, lo, hi);
     const BackView v{&own, nullptr, hi > lo ? &cr : nullptr, false, false};
     int rc = run_front_stage(h, c, stage, s);
@@ -74,13 +73,13 @@ int run_sharded_stage(tslam_handle* h, const BatchCtx& c, int stage, hipStream_t
     const bool empty = hi <= lo;           // a short batch leaves this rank no frames
     const bool pre = !empty && c.g0 + lo - 1 >= 0;   // frame lo - 1 exists
     BatchCtx cp = c;                        // the pre-pass: frame lo - 1, batch scratch at frame 0
-    cp.g0 = c.g0 + lo - 1;
+    ctx_set_first_frame(cp, c.g0 + lo - 1);
     cp.n = 1;
     BatchCtx cr = c;                        // pair split: the rig range
     BackView v{empty ? nullptr : &cb, pre ? &cp : nullptr, empty ? nullptr : &cb, true, false};   // POSE adds the rig pose
     if (h->sh_pairs) {   // pair split: this camera's pair only; the rig pose is its own step (KERNEL_RIG)
-        cb.pair0 = cp.pair0 = h->sh_cam_lo / 2;
-        cb.npair = cp.npair = 1;
+        ctx_set_views(cb, cb.cam0, cb.ncam, h->sh_cam_lo / 2, 1);
+        ctx_set_views(cp, cp.cam0, cp.ncam, h->sh_cam_lo / 2, 1);
         int rl, rh;
         shard_range(h, c.n, &rl, &rh);   // every pair's blocks of the rig range are here (tslam_shard.cpp)
         cr = range_ctx(c, rl, rh);
@@ -164,10 +163,9 @@ int tslam_import_raw(tslam_handle* h, const uint8_t* images, int64_t first_frame
     const int ncam = cam_hi - cam_lo;
     const int64_t skip = first_frame < 0 ? -first_frame : 0;   // frames before the sequence start
     c.images = images + (size_t)skip * ncam * h->W * h->H;
-    c.g0 = first_frame + skip;
+    ctx_set_first_frame(c, first_frame + skip);
     c.n = (int)(n_frames - skip);
-    c.cam0 = cam_lo;
-    c.ncam = ncam;
+    ctx_set_views(c, cam_lo, ncam, c.pair0, c.npair);
     launch_rectify_pyramid(c, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return TSLAM_OK;
@@ -309,7 +307,7 @@ int tslam_import_peers(tslam_handle* h, const uint8_t* raw, const void* streams,
     const int skip = first < 0 ? 1 : 0;   // frame -1 (before the sequence start) is not imported
     BatchCtx c = make_ctx(h);
     c.images = raw;
-    c.g0 = first + skip;
+    ctx_set_first_frame(c, first + skip);
     c.n = nr - skip;
     c.peer_S = g.S;
     c.peer_me = h->sh_rank;
@@ -370,10 +368,9 @@ int tslam_internal_import_partner(tslam_handle* h, const uint8_t* raw, const voi
     const int skip = first < 0 ? 1 : 0;   // frame -1 (before the sequence start) is not imported
     BatchCtx c = make_ctx(h);
     c.images = raw + (size_t)skip * h->W * h->H;
-    c.g0 = first + skip;
+    ctx_set_first_frame(c, first + skip);
     c.n = nf - skip;
-    c.cam0 = partner;
-    c.ncam = 1;
+    ctx_set_views(c, partner, 1, c.pair0, c.npair);
     if (c.n > 0) launch_rectify_pyramid(c, (hipStream_t)stream);
     launch_stream_blocks(make_ctx(h), false, first, nf, partner, 1, (uint8_t*)streams, (hipStream_t)stream);
     HIPCHK(hipGetLastError());

@@ -85,6 +85,19 @@ struct LevelGeom {
     int dt_total;                  // describe tiles per image
 };
 
+// k_describe's block decode as a table: for block i of an image (0 <= i < dt_total) the word
+// level | tile column << 8 | tile row << 16 (tiles of level l are dt_start[l] .. in row-major order,
+// dt_nx[l] per row), so the block finds its tile with one load instead of a level search and a division
+static inline void describe_tile_table(const LevelGeom& g, uint32_t* out) {
+    for (int l = 0; l < g.n_levels; ++l) {
+        const int end = l + 1 < g.n_levels ? g.dt_start[l + 1] : g.dt_total;
+        for (int i = g.dt_start[l]; i < end; ++i) {
+            const int local = i - g.dt_start[l], ty = local / g.dt_nx[l], tx = local - ty * g.dt_nx[l];
+            out[i] = (uint32_t)l | ((uint32_t)tx << 8) | ((uint32_t)ty << 16);
+        }
+    }
+}
+
 struct PairCalib {
     double fx, fy, cx, cy, fxb;     // fxb = fx * baseline
 };
@@ -123,7 +136,10 @@ struct BatchCtx {
     // all-to-all delivers them; the launch covers the world-1 peers' slots (not peer_me's), frames
     // peer_skip .. nbuf-1 of each (peer_S = 0: the plain [n][ncam] view above)
     int peer_S, peer_me, peer_nbuf, peer_skip;
-    int64_t g0;            // global index of the batch's first frame
+    int64_t g0;            // global index of the batch's first frame (set with ctx_set_first_frame)
+    int slot0;             // g0 % R: ring slot of the batch's first frame (batch_slot)
+    uint32_t ncam_rcp, npair_rcp;   // floor(2^32 / ncam) + 1, the same of npair (0 for 1): div_small
+    const uint32_t* dt_tile;        // [dt_total] describe tile of an image's block: level | column << 8 | row << 16
     int W, H;              // level-0 size
     // inputs
     const uint8_t* images; // [n][C][H][W] gray (RGB-D: the converted staging buffer)
@@ -183,6 +199,29 @@ struct BatchCtx {
 };
 
 static inline __host__ __device__ int ring_slot(const BatchCtx& c, int64_t g) { return (int)(g % c.R); }
+// The host side of batch_slot and div_small below: the batch's first frame with its ring slot, the
+// view's camera and pair counts with their reciprocals.
+static inline uint32_t small_rcp(int d) { return d > 1 ? (uint32_t)((1ull << 32) / (uint32_t)d) + 1u : 0u; }
+static inline void ctx_set_first_frame(BatchCtx& c, int64_t g0) {
+    c.g0 = g0;
+    c.slot0 = ring_slot(c, g0);
+}
+static inline void ctx_set_views(BatchCtx& c, int cam0, int ncam, int pair0, int npair) {
+    c.cam0 = cam0, c.ncam = ncam, c.pair0 = pair0, c.npair = npair;
+    c.ncam_rcp = small_rcp(ncam), c.npair_rcp = small_rcp(npair);
+}
+#ifdef __HIPCC__
+// Ring slot of frame f of the batch (0 <= f < n <= R) without the 64-bit modulo, and of the frame
+// before the frame in `slot`.
+__device__ __forceinline__ int batch_slot(const BatchCtx& c, int f) {
+    const int s = c.slot0 + f;
+    return s >= c.R ? s - c.R : s;
+}
+__device__ __forceinline__ int prev_slot(const BatchCtx& c, int slot) { return slot > 0 ? slot - 1 : c.R - 1; }
+// a / d for a, d >= 1 with a * d < 2^32, `rcp` = small_rcp(d) = (2^32 + e) / d with 1 <= e <= d: the
+// multiply-high is floor(a / d + a e / (2^32 d)), whose second term stays below 1 / d
+__device__ __forceinline__ int div_small(int a, uint32_t rcp) { return rcp ? (int)__umulhi((uint32_t)a, rcp) : a; }
+#endif
 
 // sharded rig: frame ranges of the ranks (tslam_ranges.h)
 #include "tslam_ranges.h"
@@ -196,7 +235,7 @@ __device__ __forceinline__ void view_image(const BatchCtx& c, int img, int* f, i
         *cam = q * c.peer_S + (r - *f * c.peer_S);
         return;
     }
-    *f = img / c.ncam;
+    *f = div_small(img, c.ncam_rcp);
     *cam = c.cam0 + (img - *f * c.ncam);
 }
 // the input image of view index img (its offset in c.images, in images)
@@ -643,12 +682,27 @@ __device__ __forceinline__ double wave_multi_sum(const double (&in)[N]) {
 // XCD-aware 1-D block mapping: blocks are dealt round-robin over the 8 XCDs, so block b runs on the
 // XCD labelled b % 8.  Give all `bpi` blocks of one image the same label, so that image's pyramid
 // lines are fetched into one L2 only.  Speed only: correctness never depends on placement.
-// Launch with xcd_grid(n_img, bpi) blocks; returns false for the padding blocks.
+// Launch with xcd_grid(n_img, bpi) blocks (xcd_grid3 below: the same order without the divisions); returns
+// false for the padding blocks.
 static inline __host__ int xcd_grid(int n_img, int bpi) { return ((n_img + 7) / 8) * 8 * bpi; }
 __device__ __forceinline__ bool xcd_image_block(int b, int n_img, int bpi, int* img, int* local) {
     const int k = b >> 3;
     *img = (k / bpi) * 8 + (b & 7);
     *local = k % bpi;
+    return *img < n_img;
+}
+// The same mapping as a 3-D grid (8, bpi, image groups): the linear workgroup order, hence the XCD
+// of every block, is xcd_grid's, and the block reads its image and local index from its
+// coordinates with no division.  Grids whose y or z extent would pass 65,535 stay 1-D (x only).
+static inline __host__ dim3 xcd_grid3(int n_img, int bpi) {
+    const int groups = (n_img + 7) / 8;
+    return bpi <= 65535 && groups <= 65535 ? dim3(8, bpi, groups) : dim3(xcd_grid(n_img, bpi));
+}
+__device__ __forceinline__ bool xcd_image_block3(int n_img, int bpi, int* img, int* local) {
+    // a 1-D grid has gridDim.y = 1 != bpi; with bpi = 1 the two decodes agree (blockIdx.z = 0, img = blockIdx.x)
+    if ((int)gridDim.y != bpi) return xcd_image_block(blockIdx.x, n_img, bpi, img, local);
+    *img = blockIdx.z * 8 + blockIdx.x;
+    *local = blockIdx.y;
     return *img < n_img;
 }
 

@@ -40,6 +40,7 @@ struct tslam_handle {
     int32_t* d_maps = nullptr;
     uint32_t* d_brief = nullptr;
     int64_t* d_wedges = nullptr;
+    uint32_t* d_dt_tile = nullptr;   // describe tile table (describe_tile_table)
     uint8_t* d_gray = nullptr;   // RGB-D: converted colour images [B][P][H][W]
     Buffer buf[TSLAM_BUF_COUNT];
     uint32_t* d_cand = nullptr;

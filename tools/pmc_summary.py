@@ -8,8 +8,8 @@ the exchange gathers) traffic = (2 * FETCH_SIZE + WRITE_SIZE) * 1024; every othe
 (gathers, scalar loads, byte reads) is reported uncorrected, (FETCH_SIZE + WRITE_SIZE) * 1024.
 Each kernel's entry names the correction it got.
 
-An optional third pass (``--sq DIR``: SQ_INSTS_VALU, SQ_WAVES) adds the VALU wave-instructions
-per launch, the numerator of the VALU-issue roofline in bench.py (peak: 256 CUs x 4 SIMD-32 x
+An optional third pass (``--sq DIR``: SQ_INSTS_VALU, SQ_WAVES, and SQ_INSTS_SALU where the pass
+collected it) adds the VALU (and scalar) wave-instructions per launch, the numerator of the VALU-issue roofline in bench.py (peak: 256 CUs x 4 SIMD-32 x
 2.4 GHz / 2 cycles per wave64 instruction = 1.2288e12 wave-instructions/s, MI355X_MICROARCH.md
 "Execution model").
 
@@ -46,6 +46,7 @@ def main():
     f, w = load(fetch), load(write)
     valu = load(sq, "SQ_INSTS_VALU") if sq else {}
     waves = load(sq, "SQ_WAVES") if sq else {}
+    salu = load(sq, "SQ_INSTS_SALU") if sq else {}
     res = {}
     for k in sorted(set(f) | set(w)):
         if not k.startswith("k_"):
@@ -60,6 +61,8 @@ def main():
         if k in valu:
             res[k]["valu_insts_per_launch"] = valu[k]
             res[k]["waves_per_launch"] = waves.get(k)
+        if k in salu:
+            res[k]["salu_insts_per_launch"] = salu[k]
     Path(out).write_text(json.dumps({"batch_frames": batch, "kernels": res}, indent=1))
     print(json.dumps(res, indent=1))
 
