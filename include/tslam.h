@@ -1115,6 +1115,55 @@ int tslam_tsdf_integrate_rect_color(tslam_handle* h, int pair, const void* color
 int tslam_tsdf_integrate_rig_color(tslam_handle* h, const tslam_tsdf_rig_camera* cams, const tslam_tsdf_rig_color* colors,
                                    int n_cams, int n_frames, int64_t first_frame, const double* world_T_base, void* stream);
 
+/* The depth archive: the dense map kept consistent with poses that change after integration (loop
+ * closure, relocalisation), by BundleFusion's re-integration (added within ABI 21: five new symbols;
+ * nothing else changes, and a handle that calls none of them behaves as before).  Spec:
+ * thor_slam_amd/dense_loop.py.  A ring on the device keeps the depth frames the volume was built
+ * from, each with the very pose-table entry it was integrated on; a frame whose pose moved by more
+ * than the thresholds is taken out of the volume at the stored entry (w' = w - 1,
+ * tsdf' = (tsdf w - obs) / w', or 0 / 0 when w' <= 0) and integrated again at the new pose, frames in
+ * archive order, each voxel loaded and stored once per call.  Exact up to f32 rounding while no
+ * voxel's weight reached max_weight; at saturation the frame counts as one of the last max_weight
+ * observations.
+ *
+ * tslam_tsdf_archive_init: a ring of `capacity` u16 depth frames of `pair`'s camera (rect != 0: the
+ *   pair's rectified camera, no table, as tslam_tsdf_integrate_rect) that keeps every frame whose
+ *   number is a multiple of `interval`.  TSLAM_EINVAL for a bad pair or capacity / interval < 1;
+ *   TSLAM_ESTATE without a volume, inside a batch, with the colour layer (it is not moved), or while
+ *   the window follows (tslam_tsdf_follow, which in turn refuses while an archive is on).  May be
+ *   called again: the ring starts empty.  tslam_reset empties the ring; tslam_tsdf_init and
+ *   tslam_tsdf_write turn the archive off (its frames are not what the new volume holds) until the
+ *   next tslam_tsdf_archive_init.
+ * tslam_tsdf_archive_integrate: tslam_tsdf_integrate of the frames first_frame + i (0 <= i <
+ *   n_frames) with (first_frame + i) % interval == 0, and only those, which then take the next ring
+ *   slots in order, the oldest frames giving way.  Poses: world_T_cam [n_frames][16] on the host (a
+ *   pose whose first element is not finite skips its frame), or NULL: the pair's device-resident
+ *   chained poses of the last batch, untracked frames skipped, premultiplied by world_T_corr (16
+ *   doubles row-major on the host; NULL: identity): world_T_cam = world_T_corr * T_abs.  A skipped
+ *   frame is not archived.  Queued on `stream`; refusals as tslam_tsdf_integrate's, TSLAM_ESTATE
+ *   without an archive, TSLAM_EINVAL for first_frame < 0.
+ * tslam_tsdf_archive_move: frames[n] and their new poses world_T_cam_new[n][16] (host).  A frame in
+ *   the ring moves when its camera centre moved by more than min_translation (metres) or
+ *   trace(R_old^T R_new) < 1 + 2 cos(min_rotation); frames not in the ring and poses whose first
+ *   element is not finite are ignored, the last entry that names a frame counts.  Selection, move
+ *   and the ring's new poses are queued on `stream` (NULL: the handle's last stream); the number of
+ *   moved frames stays on the device.  TSLAM_EINVAL unless min_translation >= 0 and
+ *   0 <= min_rotation <= pi; TSLAM_ESTATE without a volume or an archive, or inside a batch.
+ * tslam_tsdf_archive_read: synchronises.  *count: frames in the ring (0 without an archive);
+ *   frames / world_T_cam [16] of the first min(max_frames, *count) of them, oldest first: the pose
+ *   each is in the volume with; *moved_last / *moved_total: frames moved by the last call / since the
+ *   ring was emptied.  NULL pointers are skipped.
+ * tslam_tsdf_archive_read_depth: the depth image u16 [H][W] of entry `index` of that order
+ *   (synchronises). */
+int tslam_tsdf_archive_init(tslam_handle* h, int pair, int rect, int capacity, int interval);
+int tslam_tsdf_archive_integrate(tslam_handle* h, const void* depth, int64_t stride_bytes, int n_frames, int64_t first_frame,
+                                 const double* world_T_corr, const double* world_T_cam, void* stream);
+int tslam_tsdf_archive_move(tslam_handle* h, int n, const int64_t* frames, const double* world_T_cam_new, double min_translation,
+                            double min_rotation, void* stream);
+int tslam_tsdf_archive_read(tslam_handle* h, int max_frames, int64_t* frames, double* world_T_cam, int* count, int* moved_last,
+                            int64_t* moved_total);
+int tslam_tsdf_archive_read_depth(tslam_handle* h, int index, uint16_t* depth);
+
 #ifdef __cplusplus
 }
 #endif

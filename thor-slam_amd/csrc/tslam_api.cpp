@@ -470,6 +470,7 @@ int tslam_destroy(tslam_handle* h) {
         if (st) (void)hipStreamDestroy(st);
     ba_destroy(h);   // its events, then the graph cache
     register_destroy(h);
+    archive_destroy(h);
     free_all(h);
     delete h;
     return TSLAM_OK;

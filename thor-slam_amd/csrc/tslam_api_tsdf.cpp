@@ -138,6 +138,7 @@ int dense_reset(tslam_handle* h) {
             HIPCHK(hipMemset(h->tsdf.col, 0, sizeof(float) * 3 * nv));
             HIPCHK(hipMemset(h->tsdf.col_w, 0, sizeof(float) * nv));
         }
+        if (const int rc = archive_reset(h); rc != TSLAM_OK) return rc;
     }
     if (h->rnd_on) {   // the render state stays, its images do not
         const size_t n = (size_t)h->rnd_prm.width * h->rnd_prm.height * h->rnd_views;
@@ -183,6 +184,7 @@ int tslam_tsdf_init(tslam_handle* h, const double* origin, const int32_t* dims, 
     if (h->d_tsdf_win) HIPCHK(hipMemset(h->d_tsdf_win, 0, sizeof(TsdfWindow)));   // a new volume: shift 0, not following
     h->tsdf_follow_on = false;
     align_off(h);   // the align state belongs to the volume it was made for
+    archive_off(h);   // and so does the depth archive
     a.nx = dims[0];
     a.ny = dims[1];
     a.nz = dims[2];
@@ -240,6 +242,7 @@ int tslam_tsdf_follow(tslam_handle* h, const tslam_tsdf_follow_params* p) {
         h->tsdf_follow_on = false;
         return TSLAM_OK;
     }
+    if (h->arc_on) return fail(TSLAM_ESTATE, "the depth archive does not follow the window (tslam_tsdf_archive_init)");
     if (p->step < 1 || p->margin < p->step || p->margin >= TSDF_SHIFT_LIMIT) return fail(TSLAM_EINVAL, "need 1 <= step <= margin < 2^30");
     for (int a = 0; a < 3; ++a)
         if (p->anchor[a] <= -TSDF_SHIFT_LIMIT || p->anchor[a] >= TSDF_SHIFT_LIMIT) return fail(TSLAM_EINVAL, "|anchor| must be below 2^30");
@@ -439,6 +442,7 @@ int tslam_tsdf_write(tslam_handle* h, const float* tsdf, const float* weight) {
     HIPCHK(hipMemcpy(h->tsdf.tsdf, tsdf, sizeof(float) * nv, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->tsdf.weight, weight, sizeof(float) * nv, hipMemcpyHostToDevice));
     h->esdf_valid = false;
+    archive_off(h);   // the archived frames are not what this volume holds
     return TSLAM_OK;
 }
 

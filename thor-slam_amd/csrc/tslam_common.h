@@ -478,6 +478,49 @@ void launch_tsdf_align(const BatchCtx& c, int pair, int f0, const double* host_w
 void launch_align_poses(const double* wTc, const int32_t* stats, int n, double* out, hipStream_t s);
 // launch_tsdf without its pose kernel: the table `poses` [a.n][TSDF_POSE] is already on the stream
 void launch_tsdf_posed(const TsdfArgs& a, double* poses, hipStream_t s, const TsdfFollowCall* follow = nullptr);
+// The depth archive (k_tsdf_move_frames.hip; thor_slam_amd/dense_loop.py): a ring of the depth frames
+// the volume was built from, each with the very pose-table entry it was integrated on, so that a
+// frame whose pose changes is taken out of the volume at its old pose and put back at the new one.
+#define TSDF_MOVE_CHUNK 128   // selected frames whose two pose tables sit in LDS at a time (26 KB)
+struct TsdfArchiveRec {       // written on the device only
+    int64_t count;            // frames archived so far; frame number a lives in slot a % cap
+    int64_t moved_total;      // frames moved since the ring was emptied
+    int32_t n_sel;            // frames the last selection chose
+    int32_t moved_last;       // frames the last move moved
+};
+struct TsdfArchive {
+    uint8_t* depth;           // [cap] u16 [H][W] images, slot_stride bytes apart (a multiple of 16)
+    int64_t slot_stride;
+    double* pose;             // [cap][TSDF_POSE]: the entry the slot's frame is in the volume with
+    double* wTc;              // [cap][16]: the same pose as world_T_cam
+    int64_t* frame;           // [cap] frame ids
+    int cap;
+    TsdfArchiveRec* rec;
+    // the last selection, in ascending archive order
+    int32_t* sel_slot;        // [cap]
+    double* sel_old;          // [cap][TSDF_POSE]
+    double* sel_new;          // [cap][TSDF_POSE]
+    double* sel_wTc;          // [cap][16]
+};
+struct Mat4 {
+    double m[16];
+};
+// n frames (<= TSDF_MAX_FRAMES) of a call: entry i is frame `first_frame + i`, used only when that
+// is a multiple of `interval` (>= 1) and its pose is (call_pose's flag); on device poses the entry
+// is corr * T_abs (mul4_fixed's order) when has_corr.  Writes the integrator's table `poses`
+// [n][TSDF_POSE] and the same poses as world_T_cam `wTc` [n][16].
+void launch_tsdf_archive_poses(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev, int n, int64_t first_frame,
+                               int interval, bool has_corr, const Mat4& corr, double* poses, double* wTc, hipStream_t s);
+// the used entries of that table into the ring, in order, with their depth images (`depth`: entry
+// 0's, entries `stride` bytes apart; W * H pixels); slot_of [TSDF_MAX_FRAMES] is scratch
+void launch_tsdf_archive_put(const TsdfArchive& ar, const double* poses, const double* wTc, int n, int64_t first_frame,
+                             const uint8_t* depth, int64_t stride, int pixels, int32_t* slot_of, hipStream_t s);
+// The move.  req_frame [n] / req_wTc [n][16] on the device: the frames asked for and their new
+// world_T_cam; min_t2 = min_translation^2, rot_lim = 1 + 2 cos(min_rotation).  a: the volume and the
+// archive's camera (integrate_args; depth, stride, n and poses unused).  Three launches: selection,
+// k_tsdf_reintegrate over every brick (the count stays on the device), the ring's poses updated.
+void launch_tsdf_archive_move(const TsdfArchive& ar, const TsdfArgs& a, const int64_t* req_frame, const double* req_wTc, int n,
+                              double min_t2, double rot_lim, hipStream_t s);
 // dense stereo depth (k_stereo_depth.hip): n frames of one rectified pair -> disp32 (1/32 px) and
 // depth (mm), u16 [n][H][W]; win_left / win_right: u8 [n][H][W] winner maps between its two kernels
 struct StereoDepthArgs {

@@ -345,6 +345,22 @@ struct tslam_handle {
     uint8_t* d_slice_obs = nullptr;
     float* d_slice = nullptr;
     size_t slice_cap = 0;
+    // ---- tslam_api_archive.cpp ----
+    // the depth archive (tslam_tsdf_archive_*; thor_slam_amd/dense_loop.py): the ring and its last
+    // selection on the device, the camera and interval of its frames, the table of one integrate
+    // chunk as world_T_cam with the slots its entries took, and a move's requests (pinned staging,
+    // reused once the event of the copy out of it has passed, and their device copies)
+    bool arc_on = false;
+    int arc_pair = 0, arc_rect = 0, arc_interval = 1;
+    TsdfArchive arc{};
+    double* d_arc_wTc = nullptr;        // [TSDF_MAX_FRAMES][16]
+    int32_t* d_arc_slot_of = nullptr;   // [TSDF_MAX_FRAMES]
+    void* arc_pin = nullptr;            // [n] frame ids, then [n][16] poses
+    size_t arc_pin_cap = 0;
+    hipEvent_t arc_ev = nullptr;
+    bool arc_ev_armed = false;
+    void* d_arc_req = nullptr;          // the same layout on the device
+    size_t arc_req_cap = 0;
 };
 
 #define HIPCHK(expr)                                                                           \
@@ -436,6 +452,11 @@ TSLAM_INTERNAL TsdfArgs integrate_args(const tslam_handle* h, const PairCamera& 
 TSLAM_INTERNAL TsdfFollowCall follow_call(const tslam_handle* h);
 // the fields of a that describe the volume: tsdf, weight, dims, origin, s, win (the colour layer is the caller's)
 TSLAM_INTERNAL void volume_view(const tslam_handle* h, TsdfRenderArgs& a);
+
+// -- tslam_api_archive.cpp ------------------------------------------------------------------------
+TSLAM_INTERNAL int archive_reset(tslam_handle* h);     // tslam_reset: the ring is empty, the state stays
+TSLAM_INTERNAL void archive_off(tslam_handle* h);      // the archive belongs to the volume it was filled with
+TSLAM_INTERNAL void archive_destroy(tslam_handle* h);  // its event (the buffers go with the handle's)
 
 // -- tslam_api_register.cpp ------------------------------------------------------------------------
 TSLAM_INTERNAL void register_destroy(tslam_handle* h);   // its events (the buffers go with the handle's)

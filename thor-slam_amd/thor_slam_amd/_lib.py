@@ -379,6 +379,15 @@ _SIGNATURES = {
                                                        ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     "tslam_tsdf_integrate_rig_color": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                       ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "tslam_tsdf_archive_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "tslam_tsdf_archive_integrate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
+                                                    ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "tslam_tsdf_archive_move": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
+    "tslam_tsdf_archive_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                               ctypes.POINTER(ctypes.c_int64)]),
+    "tslam_tsdf_archive_read_depth": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
 }
 
 
@@ -1000,6 +1009,58 @@ class Handle:
         _check(self.lib.tslam_tsdf_integrate_rect(self.h, int(pair), ctypes.c_void_p(depth_dev_ptr), int(stride_bytes),
                                                   int(n_frames), int(first_frame),
                                                   None if poses is None else poses.ctypes.data, ctypes.c_void_p(stream)))
+
+    def tsdf_archive_init(self, capacity: int, interval: int = 1, pair: int = 0, rect: bool = False) -> None:
+        """The depth archive (thor_slam_amd/dense_loop.py): a ring of ``capacity`` depth frames of the
+        pair's camera (``rect``: its rectified camera, as ``tsdf_integrate_rect``) that keeps every
+        frame whose number is a multiple of ``interval``.  After ``tsdf_init``."""
+        _check(self.lib.tslam_tsdf_archive_init(self.h, int(pair), int(bool(rect)), int(capacity), int(interval)))
+
+    def tsdf_archive_integrate(self, depth_dev_ptr: int, stride_bytes: int, n_frames: int, first_frame: int = 0,
+                               world_T_corr: np.ndarray | None = None, world_T_cam: np.ndarray | None = None,
+                               stream: int = 0) -> None:
+        """``tsdf_integrate`` of the frames ``first_frame + i`` that are multiples of the archive's
+        interval, which are archived with the poses they went in with: host poses ``world_T_cam``
+        [n][4][4], or the last batch's tracked device poses premultiplied by ``world_T_corr`` [4][4]."""
+        poses = corr = None
+        if world_T_cam is not None:
+            poses = np.ascontiguousarray(np.asarray(world_T_cam, dtype=np.float64).reshape(-1, 4, 4))
+        if world_T_corr is not None:
+            corr = np.ascontiguousarray(np.asarray(world_T_corr, dtype=np.float64).reshape(4, 4))
+        _check(self.lib.tslam_tsdf_archive_integrate(self.h, ctypes.c_void_p(depth_dev_ptr), int(stride_bytes), int(n_frames),
+                                                     int(first_frame), None if corr is None else corr.ctypes.data,
+                                                     None if poses is None else poses.ctypes.data, ctypes.c_void_p(stream)))
+
+    def tsdf_archive_move(self, frames, world_T_cam_new: np.ndarray, min_translation: float, min_rotation: float,
+                          stream: int = 0) -> None:
+        """The archived frames among ``frames`` [n] whose pose ``world_T_cam_new`` [n][4][4] differs
+        from the stored one by more than the thresholds are taken out of the volume and integrated
+        again at the new pose (queued on ``stream``; ``tsdf_archive_read`` tells how many moved)."""
+        f = np.ascontiguousarray(np.asarray(frames, dtype=np.int64).reshape(-1))
+        T = np.ascontiguousarray(np.asarray(world_T_cam_new, dtype=np.float64).reshape(-1, 4, 4))
+        if T.shape[0] != f.shape[0]:
+            raise ValueError("one pose per frame")
+        _check(self.lib.tslam_tsdf_archive_move(self.h, int(f.shape[0]), f.ctypes.data, T.ctypes.data, float(min_translation),
+                                                float(min_rotation), ctypes.c_void_p(stream)))
+
+    def tsdf_archive_read(self, max_frames: int | None = None) -> dict:
+        """The archive, oldest frame first (synchronises): ``frames`` i64 [n], ``world_T_cam`` f64
+        [n][4][4] (the pose each frame is in the volume with), ``count`` (frames in the ring; n is at
+        most ``max_frames``), ``moved_last`` and ``moved_total``."""
+        cnt, last, total = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+        _check(self.lib.tslam_tsdf_archive_read(self.h, 0, None, None, ctypes.byref(cnt), ctypes.byref(last), ctypes.byref(total)))
+        n = cnt.value if max_frames is None else min(cnt.value, int(max_frames))
+        f = np.zeros(n, dtype=np.int64)
+        T = np.zeros((n, 4, 4), dtype=np.float64)
+        if n:
+            _check(self.lib.tslam_tsdf_archive_read(self.h, n, f.ctypes.data, T.ctypes.data, None, None, None))
+        return {"frames": f, "world_T_cam": T, "count": cnt.value, "moved_last": last.value, "moved_total": total.value}
+
+    def tsdf_archive_read_depth(self, index: int) -> np.ndarray:
+        """The depth image u16 [H][W] of entry ``index`` of ``tsdf_archive_read``'s order (synchronises)."""
+        out = np.zeros((self.height, self.width), dtype=np.uint16)
+        _check(self.lib.tslam_tsdf_archive_read_depth(self.h, int(index), out.ctypes.data))
+        return out
 
     def tsdf_integrate_rig(self, cams, n_frames: int, first_frame: int = 0, world_T_base: np.ndarray | None = None,
                            stream: int = 0) -> None:

@@ -12,6 +12,7 @@ from dataclasses import dataclass
 
 from .dense_align import DEFAULTS as ALIGN_DEFAULTS, check_align_params
 from .dense_follow import check_follow_params
+from .dense_loop import check_loop_params
 from .dense_rig import DenseCamerasError
 from .slam.interface import SlamConfig
 from .stereo_depth import check_params as check_stereo_depth_params
@@ -178,6 +179,19 @@ class HipSlamConfig(SlamConfig):
     dense_align_min_inliers: int = 200
     dense_align_max_translation_m: float = 0.1
     dense_align_max_rotation_rad: float = 0.1
+    # the dense map kept consistent with loop closure and relocalisation (thor_slam_amd/dense_loop.py):
+    # the map takes the frames that have a pose-graph node (g % loop_kf_interval == 0), on the pose
+    # the loop correction gives them, and keeps their depth in a ring of dense_loop_capacity frames on
+    # the device (512 KB each at 640 x 400); when the nodes' poses change, every archived frame whose
+    # pose moved by more than dense_loop_min_translation_m (None = half a voxel) or
+    # dense_loop_min_rotation_rad is taken out of the volume and integrated again at its new pose.
+    # Published poses are not changed.  Exact only below tsdf_max_weight observations per voxel.
+    # Needs dense_map, enable_loop_closure and one device; colour, dense_cameras, dense_follow and
+    # dense_align are refused.
+    dense_loop: bool = False
+    dense_loop_capacity: int = 1024
+    dense_loop_min_translation_m: float | None = None
+    dense_loop_min_rotation_rad: float = 0.005
     # dense stereo depth (thor_slam_amd/stereo_depth.py): on a stereo rig, pair 0's depth image is
     # computed on the device from the rectified images (candidate disparities 0 .. max_disparity - 1)
     # and feeds dense_map as an RGB-D camera's depth does (no colour layer: the images are gray, so
@@ -312,6 +326,24 @@ class HipSlamConfig(SlamConfig):
             if self.devices:
                 raise ValueError("dense_align does not run on a sharded rig (devices)")
             check_align_params(**self.dense_align_params(), max_frames=1)
+        if self.dense_loop:
+            if not self.dense_map:
+                raise ValueError("dense_loop needs dense_map=True")
+            if not self.enable_loop_closure:
+                raise ValueError("dense_loop needs enable_loop_closure=True (it follows the pose graph's corrections)")
+            if self.devices:
+                raise ValueError("dense_loop does not run on a sharded rig (devices)")
+            if self.dense_follow:
+                raise ValueError("dense_loop does not run with dense_follow: a frame that left the window cannot be moved")
+            if self.dense_align:
+                raise ValueError("dense_loop does not run with dense_align: the aligned poses have no pose-graph node")
+            if self.dense_cameras:
+                raise ValueError("dense_loop does not run with dense_cameras: the archive holds one camera")
+            if (self.dense_color and self.rgbd) or self.stereo_color:
+                raise ValueError("dense_loop needs dense_color=False and stereo_color=False: colour is not moved yet")
+            if self.stereo_depth and self.loop_kf_interval % self.stereo_depth_interval != 0:
+                raise ValueError("dense_loop: stereo_depth_interval must divide loop_kf_interval (the node frames are matched)")
+            check_loop_params(self.dense_loop_capacity, self.dense_loop_min_translation_m, self.dense_loop_min_rotation_rad)
         if not (self.ba_window == 0 or 2 <= self.ba_window <= 10):
             raise ValueError("ba_window must be 0 (off) or in [2, 10]")
         if self.ba_kf_interval < 1 or self.ba_iters < 1:

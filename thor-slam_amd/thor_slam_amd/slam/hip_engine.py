@@ -35,7 +35,11 @@ in one launch per batch (``tslam_tsdf_integrate_rig``) on the rig's body poses, 
 and for dense stereo depth alike (``thor_slam_amd/dense_rig.py``).  ``dense_follow`` lets the volume
 follow the camera in whole voxels, decided on the device once per integrated batch
 (``thor_slam_amd/dense_follow.py``); ``get_dense_map`` / ``get_esdf`` / ``get_esdf_slice`` then
-report the window's effective ``origin`` and its ``window_shift``.  ``stereo_color`` colours a
+report the window's effective ``origin`` and its ``window_shift``.  ``dense_loop`` keeps the dense
+map consistent with loop closure and relocalisation (``thor_slam_amd/dense_loop.py``): the map takes
+the pose-graph node frames, on the loop-corrected pose, keeps their depth in an archive on the device,
+and after the nodes' poses changed the archived frames that moved are taken out of the volume and
+integrated again at their new poses; ``get_dense_archive`` reports the archive.  ``stereo_color`` colours a
 stereo rig's dense map from the source's centre colour camera (``thor_slam_amd/depth_register.py``):
 ``set_color_camera`` after ``initialize``, ``push_color`` before the ``process_frames`` call of the
 frame the image belongs to; the colour is registered to the stereo depth on the device, and
@@ -465,6 +469,7 @@ class HipSlamEngine(SlamEngine):
         self._in_flight = 0                       # batches submitted, not yet published
         self._shard: dict | None = None           # sharded rig (config.devices): handles, group, inputs
         self._sd_last: dict = {}                  # pair -> (slot, timestamp) of its newest stereo depth image
+        self._dense_loop_seen = 0                 # dense_loop: corrections of the pose graph the map has followed
         self._dense_pairs: tuple = ()             # config.dense_cameras resolved (() = pair 0 on its own pose)
         # stereo_color: pair -> its colour camera (set_color_camera): pinned staging and device images
         # per batch slot, per slot whether a colour image in time was pushed, the timestamp of a
@@ -545,6 +550,9 @@ class HipSlamEngine(SlamEngine):
                 if cfg.dense_align:   # frame-to-model alignment before integration (thor_slam_amd/dense_align.py)
                     self._handle.tsdf_align_init(pair=0, rect=bool(cfg.stereo_depth), max_frames=cfg.batch_size,
                                                  **cfg.dense_align_params())
+                if cfg.dense_loop:   # the node frames' depth is kept, to follow the pose graph (thor_slam_amd/dense_loop.py)
+                    self._handle.tsdf_archive_init(cfg.dense_loop_capacity, interval=cfg.loop_kf_interval, pair=0,
+                                                   rect=bool(cfg.stereo_depth))
                 if cfg.stereo_depth:   # a stereo rig: the depth comes from the dense matcher (slots per camera)
                     self._handle.stereo_depth_init(max_frames=cfg.batch_size * max(1, len(self._dense_pairs)),
                                                    uniqueness=cfg.stereo_depth_uniqueness,
@@ -557,6 +565,7 @@ class HipSlamEngine(SlamEngine):
             self._sd_last = {}
             self._color_cams, self._color_zero, self._reg_last = {}, None, {}
             self._view_key = None   # get_dense_view's camera (size, intrinsics, range) on the handle
+            self._dense_loop_seen = 0   # corrections of the pose graph the dense map has followed
             self._loop = None
             if cfg.enable_loop_closure and cfg.devices and cfg.rgbd:
                 # rank 0's ring holds only its own cameras' features (no state gather): no rig-wide
@@ -803,6 +812,7 @@ class HipSlamEngine(SlamEngine):
         if isinstance(self._loop, _AsyncLoop):
             with self._map_lock:
                 self._loop.advance(until=1 << 62)
+                self._dense_loop_follow()
 
     # -- IMU fusion -------------------------------------------------------
     @staticmethod
@@ -1096,6 +1106,9 @@ class HipSlamEngine(SlamEngine):
         if not self._config.dense_map:
             return
         dense = self._dense_pairs
+        if self._config.dense_loop:
+            self._integrate_depth_archived(records_ptr, n, stream, cams_per_frame, stamps)
+            return
         if self._config.stereo_depth:
             g0 = self._handle.frames_done - n
             every = self._config.stereo_depth_interval
@@ -1157,6 +1170,55 @@ class HipSlamEngine(SlamEngine):
         else:
             self._handle.tsdf_integrate(records_ptr + 3 * hw, stride, n,
                                         first_frame=self._handle.frames_done - n, pair=0, stream=stream)
+
+    def _integrate_depth_archived(self, records_ptr: int, n: int, stream: int, cams_per_frame: int | None,
+                                  stamps: list | None) -> None:
+        """``dense_loop``: of the batch's frames only those that can have a pose-graph node
+        (g % loop_kf_interval == 0, tracked; frame 0 initialises and has none) go into the volume, on
+        the loop graph's current correction times their tracked pose, and into the depth archive."""
+        cfg, h = self._config, self._handle
+        g0 = h.frames_done - n
+        corr = None if self._loop is None else self._loop.corr
+        every = cfg.loop_kf_interval
+        if cfg.stereo_depth:   # only the node frames are matched
+            depth_ptr, _, frame_bytes = h.stereo_depth_buffers()
+            for g in range(g0, g0 + n):
+                if g % every == 0 and g > 0:
+                    h.stereo_depth(g, 1, pair=0, stream=stream)
+                    h.tsdf_archive_integrate(depth_ptr, frame_bytes, 1, first_frame=g, world_T_corr=corr, stream=stream)
+                    self._sd_last[0] = (0, None if stamps is None else float(stamps[g - g0]))
+            return
+        hw = self._rects[0].width * self._rects[0].height
+        stride = 5 * hw * (cams_per_frame or len(self._pairs))
+        skip = 1 if g0 == 0 else 0
+        if n > skip:
+            h.tsdf_archive_integrate(records_ptr + 3 * hw + skip * stride, stride, n - skip, first_frame=g0 + skip,
+                                     world_T_corr=corr, stream=stream)
+
+    def _dense_loop_follow(self) -> None:
+        """After the pose graph's nodes changed (a loop closed, a segment relocalised): every node's
+        frame and pose to the archive, which moves the frames whose pose changed by more than the
+        thresholds; queued on the handle's last stream, so before the next batch's integration."""
+        cfg, lp = self._config, self._loop
+        if not (cfg.dense_map and cfg.dense_loop) or lp is None or self._handle is None:
+            return
+        seen = len(lp.loops) + len(getattr(lp, "relocs", ()))
+        if seen == self._dense_loop_seen:
+            return
+        self._dense_loop_seen = seen
+        min_t = 0.5 * cfg.voxel_size if cfg.dense_loop_min_translation_m is None else cfg.dense_loop_min_translation_m
+        self._handle.tsdf_archive_move(lp.frames, np.array(lp.T).reshape(-1, 4, 4), min_t, cfg.dense_loop_min_rotation_rad)
+
+    def get_dense_archive(self) -> dict | None:
+        """The depth archive of ``dense_loop``, oldest frame first: ``frames`` i64 [n], ``world_T_cam``
+        f64 [n][4][4] (the pose each frame is in the dense map with, in the volume's frame),
+        ``moved_last`` and ``moved_total`` (frames moved by the last correction, and since the start
+        or the last reset).  None unless ``dense_loop`` is on.  Synchronises."""
+        if not (self._config.dense_map and self._config.dense_loop) or self._handle is None:
+            return None
+        self.flush()
+        a = self._handle.tsdf_archive_read()
+        return {k: a[k] for k in ("frames", "world_T_cam", "moved_last", "moved_total")}
 
     def get_depth_image(self, pair: int = 0) -> tuple | None:
         """(depth u16 [H][W] in mm of pair ``pair``'s rectified left camera, timestamp) of the newest
@@ -1387,6 +1449,7 @@ class HipSlamEngine(SlamEngine):
     def _publish(self, res: dict, stamps: list[float], g0: int) -> None:
         with self._map_lock:
             self._publish_locked(res, stamps, g0)
+            self._dense_loop_follow()
 
     def _publish_locked(self, res: dict, stamps: list[float], g0: int) -> None:
         entry = next((e for e in self._imu_batches if e["res"] is None), None) if self._imu is not None else None
@@ -1671,6 +1734,7 @@ class HipSlamEngine(SlamEngine):
         self._kf_ine = None
         self._sd_last = {}
         self._reg_last = {}
+        self._dense_loop_seen = 0
         for cc in self._color_cams.values():
             cc["has"], cc["pushed"] = [False] * len(cc["has"]), None
         if self._imu is not None:
