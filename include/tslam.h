@@ -629,6 +629,11 @@ int tslam_select_mode(tslam_handle* h, int mode, int resident_cap);
  * capacity; N > 0: at most N positions of a window are merged, the rest take the direct path in the
  * same launch. */
 int tslam_match_mode(tslam_handle* h, int mode, int merge_cap);
+/* Test hook for the descriptor kernel's keypoint list (results are identical for every value).
+ * list_cap 0 (default): the built-in capacity; N > 0: a tile lists at most N of the y-sorted
+ * records of its rows at a time and serves the rest in further chunks, as it does by itself where
+ * the rows hold more records than the list. */
+int tslam_describe_mode(tslam_handle* h, int list_cap);
 /* Path counters of the matcher (synchronises).  The first call switches counting on and returns
  * zeros; every call returns the counts since the previous one and clears them.  counters16: per
  * mode (stereo 0..7, temporal 8..15) [0] train minima merged in LDS, [1] sent directly, [2] global

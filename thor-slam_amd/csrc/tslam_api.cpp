@@ -230,6 +230,7 @@ BatchCtx make_ctx(tslam_handle* h) {
     c.pp.seed = h->prm.ransac_seed;
     c.fast_threshold = h->prm.fast_threshold;
     c.margin = h->prm.edge_margin;
+    c.dt_list_cap = h->dt_list_cap > 0 ? std::min(h->dt_list_cap, TS_DT_LIST) : TS_DT_LIST;
     ctx_set_views(c, h->sh_cam_lo, h->sh_cam_hi - h->sh_cam_lo, 0, h->P);
     c.match_modes = 3;
     c.reloc = 0;
@@ -887,6 +888,12 @@ int tslam_match_mode(tslam_handle* h, int mode, int merge_cap) {
     if (!h || mode < 0 || mode > 2 || merge_cap < 0) return fail(TSLAM_EINVAL, "bad handle, match mode or capacity");
     h->match_mode = mode;
     h->match_cap = merge_cap;
+    return TSLAM_OK;
+}
+
+int tslam_describe_mode(tslam_handle* h, int list_cap) {
+    if (!h || list_cap < 0) return fail(TSLAM_EINVAL, "bad handle or list capacity");
+    h->dt_list_cap = list_cap;
     return TSLAM_OK;
 }
 

@@ -196,6 +196,7 @@ struct BatchCtx {
     MatchParams mp;
     PoseParams pp;
     int fast_threshold, margin;
+    int dt_list_cap;       // k_describe: y-sorted positions listed at a time, 1 .. TS_DT_LIST (tslam_describe_mode)
 };
 
 static inline __host__ __device__ int ring_slot(const BatchCtx& c, int64_t g) { return (int)(g % c.R); }

@@ -22,3 +22,7 @@
 #define TS_DT_RAW_ROWS (TS_DT_H + 30)       // raw level: orientation disc radius 15
 #define TS_DT_RAW_P 160                     // raw tile pitch: columns [x0 - 16, x0 + 144), 10 x 16 B
 #define TS_DT_SMO_ROWS (TS_DT_H + 36)       // smoothed level: rotated BRIEF radius 18
+// k_describe's keypoint list: y-sorted positions of the tile's rows listed at a time (8-byte
+// entries; a tile's rows rarely hold more than 320, more are served in chunks).  4 KB keeps the
+// block at 40,100 B of LDS = 4 blocks per CU.
+#define TS_DT_LIST 512

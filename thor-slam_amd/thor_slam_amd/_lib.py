@@ -275,6 +275,7 @@ _SIGNATURES = {
     "tslam_ba_defer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "tslam_select_mode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
     "tslam_match_mode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
+    "tslam_describe_mode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "tslam_match_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int)]),
     "tslam_detect_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int]),
     "tslam_ba_inertial": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
@@ -1477,6 +1478,11 @@ class Handle:
         """``tslam_match_mode`` (test hook): k_match's train-side flush, ``auto`` / ``direct`` (every wave's
         own atomics) / ``merged`` (per block in LDS), and a cap on the merged window positions (0: built in)."""
         _check(self.lib.tslam_match_mode(self.h, MATCH_MODE[mode], int(merge_cap)))
+
+    def describe_mode(self, list_cap: int = 0) -> None:
+        """``tslam_describe_mode`` (test hook): a cap on the y-sorted positions a k_describe tile lists at
+        a time (0: built in); a tile whose rows hold more is served in chunks."""
+        _check(self.lib.tslam_describe_mode(self.h, int(list_cap)))
 
     def match_counters(self) -> dict:
         """``tslam_match_counters``: the matcher's path counts since the last call (the first call switches
