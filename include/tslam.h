@@ -675,6 +675,14 @@ int tslam_relocalize(tslam_handle* h, int pair, int64_t frame, double* cam_T_wor
  * rig's; pair_stats[P][8] per pair).  A map seen by any one pair relocalises the rig. */
 int tslam_relocalize_rig(tslam_handle* h, int64_t frame, double* body_T_world, double* cov, int32_t* stats,
                          int32_t* pair_stats);
+/* tslam_reloc_read (added within ABI 21: a new symbol, nothing else changes): what the last
+ * tslam_relocalize, tslam_loop_verify or tslam_relocalize_rig left for `pair` (synchronises):
+ * match[K] = the map (or entry landmark) index of every keypoint, -1 for "no match" and for
+ * keypoints past their level's count; *n_corr = stats[1]; corr[K][8], of which the first *n_corr
+ * rows are written: X Y Z du dv bx by bz as TSLAM_BUF_CORR, in keypoint order.  Any pointer may be
+ * NULL.  TSLAM_ESTATE without relocalisation scratch (no tslam_map_upload / tslam_loop_init yet),
+ * TSLAM_EINVAL for a bad pair.  The single-pair calls use pair 0's scratch whatever their `pair`. */
+int tslam_reloc_read(tslam_handle* h, int pair, int32_t* match, double* corr, int* n_corr);
 
 /* Loop closure + keyframe pose graph (the reference only forwards
  * SlamConfig.enable_loop_closure, thor_slam/slam/interface.py:155-156, to cuVSLAM).  Spec and CPU

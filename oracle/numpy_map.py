@@ -53,15 +53,29 @@ def match_map(feat: dict, map_desc: np.ndarray, cfg, chunk: int = 256) -> np.nda
     return out
 
 
-def relocalize(feat: dict, map_xyz: np.ndarray, map_desc: np.ndarray, intr, cfg, frame: int) -> dict:
+def correspondences(feat: dict, m: np.ndarray, map_xyz: np.ndarray, intr) -> dict:
+    """The matches ``m`` [K] (map index or -1) as 3D-2D correspondences in keypoint order: the map
+    point, the level-0 keypoint position as (cx - u, cy - v), and its unit bearing (bx, by, bz) =
+    (x, y, 1) / |(x, y, 1)| with x = (u - cx) / fx, y = (v - cy) / fy, |.| = sqrt((x x + y y) + 1)."""
     fx, fy, cx, cy = intr
-    m = match_map(feat, map_desc, cfg)
     j = np.nonzero(m >= 0)[0]
     kp = feat["kp"]
     u, v = level0_coords(kp["x"][j], kp["y"][j], kp["level"][j])
-    xyz = map_xyz[m[j]]
-    corr = {"X": xyz[:, 0], "Y": xyz[:, 1], "Z": xyz[:, 2], "du": cx - u, "dv": cy - v, "u": u, "v": v,
-            "j": j, "i": m[j]}
+    xyz = np.asarray(map_xyz, dtype=np.float64).reshape(-1, 3)[m[j]]
+    x, y = (u - cx) / fx, (v - cy) / fy
+    nn = np.sqrt((x * x + y * y) + 1.0)
+    return {"X": xyz[:, 0], "Y": xyz[:, 1], "Z": xyz[:, 2], "du": cx - u, "dv": cy - v, "u": u, "v": v,
+            "bx": x / nn, "by": y / nn, "bz": 1.0 / nn, "j": j, "i": m[j]}
+
+
+def corr_rows(corr: dict) -> np.ndarray:
+    """``correspondences`` in the device's row layout [n][8]: X Y Z du dv bx by bz."""
+    return np.stack([corr[k] for k in ("X", "Y", "Z", "du", "dv", "bx", "by", "bz")], axis=1).reshape(-1, 8)
+
+
+def relocalize(feat: dict, map_xyz: np.ndarray, map_desc: np.ndarray, intr, cfg, frame: int) -> dict:
+    m = match_map(feat, map_desc, cfg)
+    corr = correspondences(feat, m, map_xyz, intr)
     res = estimate_pose(corr, intr, cfg, frame)
     res["matches"] = m
     res["corr"] = corr

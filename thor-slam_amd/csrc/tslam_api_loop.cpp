@@ -120,6 +120,8 @@ static int reloc_solve(tslam_handle* h, int pair, int64_t frame, const double* m
     if (M == 0) {
         const int32_t st[8] = {1, 0, 0, 0, -1, (int32_t)frame, 0, 0};
         HIPCHK(hipMemcpy(h->d_rl_stats, st, sizeof(st), hipMemcpyHostToDevice));
+        // no kernel runs: the matches of an earlier, larger map must not stay readable (tslam_reloc_read)
+        HIPCHK(hipMemsetAsync(h->d_rl_match, 0xFF, sizeof(int32_t) * (size_t)h->g.K, s));
     } else {
         launch_reloc(c, pair, frame, map_xyz, map_desc, (int)M, h->d_rl_match, h->d_rl_corr, h->d_rl_stats,
                      h->d_rl_pose, h->d_rl_ransac, h->d_rl_hyp, s);
@@ -202,6 +204,7 @@ int tslam_relocalize_rig(tslam_handle* h, int64_t frame, double* body_T_world, d
         HIPCHK(hipMemcpy(h->d_rl_stats, st.data(), sizeof(int32_t) * TS_STATS_INTS * P, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(h->d_rl_rig_stats, st.data() + (size_t)P * TS_STATS_INTS, sizeof(int32_t) * TS_STATS_INTS,
                          hipMemcpyHostToDevice));
+        HIPCHK(hipMemsetAsync(h->d_rl_match, 0xFF, sizeof(int32_t) * (size_t)h->g.K * P, s));   // as reloc_solve
     } else {
         launch_reloc_rig(c, frame, h->d_map_xyz, h->d_map_desc, (int)h->map_n, h->d_rl_match, h->d_rl_corr, h->d_rl_stats,
                          h->d_rl_pose, h->d_rl_ransac, h->d_rl_hyp, h->d_rl_rig_pose, h->d_rl_rig_stats, s);
@@ -220,6 +223,26 @@ int tslam_relocalize_rig(tslam_handle* h, int64_t frame, double* body_T_world, d
     if (cov) memcpy(cov, pose + 32, 36 * sizeof(double));
     if (stats) memcpy(stats, st, sizeof(st));
     if (pair_stats) HIPCHK(hipMemcpy(pair_stats, h->d_rl_stats, sizeof(int32_t) * TS_STATS_INTS * P, hipMemcpyDeviceToHost));
+    return TSLAM_OK;
+}
+
+int tslam_reloc_read(tslam_handle* h, int pair, int32_t* match, double* corr, int* n_corr) {
+    if (!h) return fail(TSLAM_EINVAL, "null handle");
+    BA_FLUSH(h);
+    if (!h->d_rl_match) return fail(TSLAM_ESTATE, "no relocalisation scratch (tslam_map_upload / tslam_loop_init)");
+    if (pair < 0 || pair >= h->P) return fail(TSLAM_EINVAL, "bad pair");
+    HIPCHK(hipSetDevice(h->device));
+    if (loop_quiesce(h) != TSLAM_OK) return TSLAM_EHIP;
+    HIPCHK(hipDeviceSynchronize());
+    const size_t K = h->g.K;
+    int32_t st[TS_STATS_INTS];
+    HIPCHK(hipMemcpy(st, h->d_rl_stats + (size_t)pair * TS_STATS_INTS, sizeof(st), hipMemcpyDeviceToHost));
+    const size_t n = (size_t)std::min<int64_t>(std::max<int32_t>(st[1], 0), (int64_t)K);
+    if (match) HIPCHK(hipMemcpy(match, h->d_rl_match + (size_t)pair * K, sizeof(int32_t) * K, hipMemcpyDeviceToHost));
+    if (corr && n)
+        HIPCHK(hipMemcpy(corr, h->d_rl_corr + (size_t)pair * K * TS_CORR_DOUBLES, sizeof(double) * TS_CORR_DOUBLES * n,
+                         hipMemcpyDeviceToHost));
+    if (n_corr) *n_corr = (int)n;
     return TSLAM_OK;
 }
 

@@ -268,7 +268,9 @@ _SIGNATURES = {
     "tslam_relocalize": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 3),
     "tslam_relocalize_rig": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p]),
-    "tslam_ba_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 6),
+    "tslam_reloc_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.POINTER(ctypes.c_int)]),
+    "tslam_ba_read":(ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 6),
     "tslam_ba_replay_schur": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                               ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "tslam_ba_split_solve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
@@ -873,6 +875,16 @@ class Handle:
         _check(self.lib.tslam_relocalize_rig(self.h, int(frame), T.ctypes.data, cov.ctypes.data, st.ctypes.data,
                                              pst.ctypes.data))
         return {"T": T, "cov": cov, "stats": st, "pair_stats": pst}
+
+    def reloc_read(self, pair: int = 0) -> dict:
+        """What the last ``relocalize`` / ``loop_verify`` / ``relocalize_rig`` left for ``pair``
+        (synchronises): match [K] i32 (map index or -1 per keypoint) and corr [n_corr][8] f64 (X Y Z du
+        dv bx by bz, keypoint order)."""
+        match = np.full(self.K, -1, dtype=np.int32)
+        corr = np.zeros((self.K, 8))
+        n = ctypes.c_int()
+        _check(self.lib.tslam_reloc_read(self.h, int(pair), match.ctypes.data, corr.ctypes.data, ctypes.byref(n)))
+        return {"match": match, "corr": corr[:n.value]}
 
     # -- loop closure + pose graph (SURVEY.md §8f items 1, 3) --------------------------------
     def loop_init(self, max_keyframes: int = 1024, signature: int = 256) -> None:
