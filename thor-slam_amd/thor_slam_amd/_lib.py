@@ -1524,7 +1524,7 @@ class Handle:
         return out
 
     def ba_graph(self, enable: bool) -> None:
-        """Pair windows' keyframe chains from captured hipGraphs (default) or direct launches (tslam.h)."""
+        """Pair windows' keyframe chains by direct launches (default) or, opt-in, from captured hipGraphs (tslam.h)."""
         _check(self.lib.tslam_ba_graph(self.h, int(bool(enable))))
 
     def ba_split_solve(self, split: bool) -> None:
