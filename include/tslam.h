@@ -1046,6 +1046,50 @@ int tslam_tsdf_align_buffers(tslam_handle* h, void** world_T_cam, void** stats);
 int tslam_tsdf_integrate_aligned(tslam_handle* h, const void* color, const void* depth, int64_t stride_bytes, int n_frames,
                                  void* stream);
 
+/* Dynamic objects kept out of the dense map: the free-space depth mask (added within ABI 21: new
+ * symbols and a struct, nothing else changes, and a handle that calls none of them behaves as
+ * before).  Spec: thor_slam_amd/dense_dynamic.py.  A depth pixel whose point lands in a voxel the map
+ * has reliably seen empty (weight >= min_free_weight and tsdf >= free_fraction * truncation) is a
+ * candidate for a moving object; the candidates are opened by open_radius pixels (erosion, then
+ * dilation, with squares; what lies outside the image counts as 0) and dilated by dilate_radius.  The
+ * outputs are that mask and a copy of the depth image, on the pair's rectified grid, with the masked
+ * pixels zeroed.  The copy goes to tslam_tsdf_integrate_rect (stride 2 * W * H, the same poses),
+ * which follows the rolling window as before; there is no integrate call of its own.  Every frame of
+ * a call is judged against the volume as the stream finds it at that call.
+ *
+ * tslam_tsdf_dynamic_init: the camera (`pair`; rect != 0: the depth lives in the pair's rectified
+ *   camera, as for tslam_tsdf_integrate_rect; else it is looked up through the raw camera's table,
+ *   as tslam_tsdf_integrate looks it up), the parameters and the most frames of one call (1..256).
+ *   NULL params frees the state.  TSLAM_ESTATE without a volume or inside a batch; TSLAM_EINVAL
+ *   unless min_free_weight > 0, 0 < free_fraction <= 1 (both finite), 0 <= open_radius <= 4,
+ *   0 <= dilate_radius <= 8 and reserved 0.  A refused call changes nothing.  tslam_reset keeps the
+ *   state and clears its images; tslam_tsdf_init frees it.
+ * tslam_tsdf_dynamic: n_frames (0..max_frames) depth images (device, u16 mm, stride_bytes apart) on
+ *   `stream` (NULL: the handle's last stream) into slots 0.. ; frames and poses exactly as in
+ *   tslam_tsdf_align (host poses staged as tslam_tsdf_render stages them, a pose whose first element
+ *   is not finite is UNUSED; NULL: frames first_frame.. of the last batch with the pair's
+ *   device-resident chained poses, untracked frames UNUSED).  Nothing waits.
+ * tslam_tsdf_dynamic_buffers: the device pointers of the slots' depth (u16 [max_frames][H][W]), mask
+ *   (u8, 0 or 1) and stats (i32 [max_frames][4]) and the bytes of one frame's depth and mask; any
+ *   argument may be NULL.
+ * tslam_tsdf_dynamic_read: one slot (synchronises); NULL pointers are skipped.  stats [4]: status,
+ *   valid pixels (0 < depth <= the volume's max_dist), candidates, valid pixels under the mask.  An
+ *   UNUSED frame has an empty mask, the looked-up depth as it is and counts of 0. */
+#define TSLAM_DYNAMIC_OK 0
+#define TSLAM_DYNAMIC_UNUSED 1     /* a NaN host pose or an untracked batch frame */
+typedef struct {
+    double min_free_weight;   /* a voxel counts as seen from this weight on (> 0) */
+    double free_fraction;     /* ... and as free from this fraction of the truncation distance on, in (0, 1] */
+    int32_t open_radius;      /* pixels, 0..4 */
+    int32_t dilate_radius;    /* pixels, 0..8 */
+    int32_t reserved[4];      /* 0 */
+} tslam_tsdf_dynamic_params;
+int tslam_tsdf_dynamic_init(tslam_handle* h, int pair, int rect, const tslam_tsdf_dynamic_params* params, int max_frames);
+int tslam_tsdf_dynamic(tslam_handle* h, const void* depth, int64_t stride_bytes, int n_frames, int64_t first_frame,
+                       const double* world_T_cam, void* stream);
+int tslam_tsdf_dynamic_buffers(tslam_handle* h, void** depth, void** mask, void** stats, int64_t* frame_bytes);
+int tslam_tsdf_dynamic_read(tslam_handle* h, int frame, uint16_t* depth, uint8_t* mask, int32_t* stats);
+
 /* Depth registration: the depth of a pair's rectified left camera forward-warped into a colour
  * camera with a z-buffer, so that a stereo rig with a centre colour camera gets a coloured dense map
  * and depth aligned to that camera (added within ABI 21: eight new symbols and two structs; nothing

@@ -147,7 +147,7 @@ int dense_reset(tslam_handle* h) {
         if (h->d_rnd_normal) HIPCHK(hipMemset(h->d_rnd_normal, 0, sizeof(float) * 3 * n));
         if (h->d_rnd_color) HIPCHK(hipMemset(h->d_rnd_color, 0, 3 * n));
     }
-    return TSLAM_OK;
+    return dynamic_reset(h);   // and so does the free-space mask's
 }
 
 int stage_poses(const double* host, int n, double* staging, hipStream_t s, const double** staged) {
@@ -184,6 +184,7 @@ int tslam_tsdf_init(tslam_handle* h, const double* origin, const int32_t* dims, 
     if (h->d_tsdf_win) HIPCHK(hipMemset(h->d_tsdf_win, 0, sizeof(TsdfWindow)));   // a new volume: shift 0, not following
     h->tsdf_follow_on = false;
     align_off(h);   // the align state belongs to the volume it was made for
+    dynamic_off(h);   // and the free-space mask's state
     archive_off(h);   // and so does the depth archive
     a.nx = dims[0];
     a.ny = dims[1];

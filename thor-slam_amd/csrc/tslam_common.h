@@ -477,6 +477,35 @@ void launch_tsdf_align(const BatchCtx& c, int pair, int f0, const double* host_w
                        const TsdfAlignArgs& a, double* poses, hipStream_t s);
 // the aligned poses as the integrator's table
 void launch_align_poses(const double* wTc, const int32_t* stats, int n, double* out, hipStream_t s);
+// The free-space depth mask (k_tsdf_dynamic.hip; thor_slam_amd/dense_dynamic.py): n frames of one
+// camera against the volume as the stream finds it; depth that lands in voxels seen free is masked.
+#define DYNAMIC_STATS 4      // status (0 OK, 1 UNUSED), valid pixels, candidates, valid pixels under the mask
+#define DYNAMIC_MAX_OPEN 4   // open_radius and dilate_radius at most: the clean-up reaches 2 * 4 + 8 = 16 < 64 bits
+#define DYNAMIC_MAX_DILATE 8
+struct TsdfDynamicArgs {
+    const float* tsdf;
+    const float* weight;
+    int nx, ny, nz;
+    double ox, oy, oz, s;
+    const TsdfWindow* win;     // as TsdfArgs::win
+    const uint8_t* depth;      // frame 0's depth (u16 mm), frames `stride` bytes apart
+    int64_t stride;
+    int n;                     // frames
+    int W, H;
+    double fx, fy, cx, cy;
+    const int32_t* map;        // as TsdfArgs::map
+    double max_dist;           // the volume's
+    double min_free_weight, thr;   // thr = free_fraction * trunc, rounded once on the host
+    int open_radius, dilate_radius;
+    const double* poses;       // [n][TSDF_POSE]: world_T_cam R rows (9), centre (3), use flag
+    uint64_t* bits;            // scratch: per (frame, row, 64 columns) the candidates' word and the valid pixels' word
+    uint16_t* out_depth;       // out: [n][H][W]
+    uint8_t* out_mask;         // out: [n][H][W]
+    int32_t* stats;            // out: [n][DYNAMIC_STATS]
+};
+// pair, f0, host_wTc_dev and poses as launch_tsdf_render
+void launch_tsdf_dynamic(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev, const TsdfDynamicArgs& a,
+                         double* poses, hipStream_t s);
 // launch_tsdf without its pose kernel: the table `poses` [a.n][TSDF_POSE] is already on the stream
 void launch_tsdf_posed(const TsdfArgs& a, double* poses, hipStream_t s, const TsdfFollowCall* follow = nullptr);
 // The depth archive (k_tsdf_move_frames.hip; thor_slam_amd/dense_loop.py): a ring of the depth frames

@@ -290,6 +290,18 @@ struct tslam_handle {
     int32_t* d_aln_stats = nullptr;   // [aln_frames][ALIGN_STATS]
     double* d_aln_resid = nullptr;    // [aln_frames][2]
     double* d_aln_neq = nullptr;      // [aln_frames][28]
+    // ---- tslam_api_dynamic.cpp ----
+    // the free-space depth mask (tslam_tsdf_dynamic_*): parameters, the camera of its frames, the
+    // call's pose table and staged host poses, the candidate words and the outputs [dyn_frames][H][W]
+    bool dyn_on = false;
+    tslam_tsdf_dynamic_params dyn_prm{};
+    int dyn_pair = 0, dyn_rect = 0, dyn_frames = 0;
+    double* d_dyn_poses = nullptr;    // [TSDF_MAX_FRAMES][TSDF_POSE]
+    double* d_dyn_wTc = nullptr;      // [TSDF_MAX_FRAMES][16] host poses staged
+    uint64_t* d_dyn_bits = nullptr;   // [dyn_frames][H][(W + 63) / 64][2]: candidates, valid pixels
+    uint16_t* d_dyn_depth = nullptr;
+    uint8_t* d_dyn_mask = nullptr;
+    int32_t* d_dyn_stats = nullptr;   // [dyn_frames][DYNAMIC_STATS]
     // ---- tslam_api_stereo.cpp ----
     // dense stereo depth (tslam_stereo_depth_*): parameters, output slots and winner-map scratch
     bool sd_on = false;
@@ -465,3 +477,7 @@ TSLAM_INTERNAL void register_destroy(tslam_handle* h);   // its events (the buff
 
 // -- tslam_api_render.cpp --------------------------------------------------------------------------
 TSLAM_INTERNAL void align_off(tslam_handle* h);   // the align state belongs to the volume it was made for
+
+// -- tslam_api_dynamic.cpp -------------------------------------------------------------------------
+TSLAM_INTERNAL void dynamic_off(tslam_handle* h);    // the mask state belongs to the volume it was made for
+TSLAM_INTERNAL int dynamic_reset(tslam_handle* h);   // tslam_reset: the state stays, its images do not

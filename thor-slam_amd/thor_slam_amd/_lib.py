@@ -163,6 +163,14 @@ class TsdfAlignParams(ctypes.Structure):
     ]
 
 
+class TsdfDynamicParams(ctypes.Structure):
+    """tslam_tsdf_dynamic_params: the rule of ``Handle.tsdf_dynamic`` (thor_slam_amd/dense_dynamic.py)."""
+    _fields_ = [
+        ("min_free_weight", ctypes.c_double), ("free_fraction", ctypes.c_double), ("open_radius", ctypes.c_int32),
+        ("dilate_radius", ctypes.c_int32), ("reserved", ctypes.c_int32 * 4),
+    ]
+
+
 def camera_desc(cam) -> CameraDesc:
     """A ``CameraConfig`` (intrinsics + world extrinsics) as a ``tslam_camera_desc``."""
     d = CameraDesc()
@@ -367,6 +375,14 @@ _SIGNATURES = {
                                                 ctypes.POINTER(ctypes.c_void_p)]),
     "tslam_tsdf_integrate_aligned": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                                     ctypes.c_int, ctypes.c_void_p]),
+    "tslam_tsdf_dynamic_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]),
+    "tslam_tsdf_dynamic": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                          ctypes.c_void_p, ctypes.c_void_p]),
+    "tslam_tsdf_dynamic_buffers": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
+                                                  ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                                  ctypes.c_void_p]),
+    "tslam_tsdf_dynamic_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p]),
     "tslam_depth_register_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]),
     "tslam_depth_register": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                             ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
@@ -1225,6 +1241,55 @@ class Handle:
         _check(self.lib.tslam_tsdf_integrate_aligned(self.h, ctypes.c_void_p(color_dev_ptr) if color_dev_ptr else None,
                                                      ctypes.c_void_p(depth_dev_ptr), int(stride_bytes), int(n_frames),
                                                      ctypes.c_void_p(stream)))
+
+    # -- the free-space depth mask (thor_slam_amd/dense_dynamic.py) -------------------------------
+    def tsdf_dynamic_init(self, pair: int = 0, rect: bool = False, max_frames: int = 1, enable: bool = True, **params) -> None:
+        """The camera (``pair``; ``rect``: the depth is the rectified camera's), the most frames of
+        one ``tsdf_dynamic`` call and the rule's parameters (``dense_dynamic.DEFAULTS``); after
+        ``tsdf_init``.  ``enable`` False frees the state."""
+        from .dense_dynamic import DEFAULTS
+
+        if not enable:
+            _check(self.lib.tslam_tsdf_dynamic_init(self.h, 0, 0, None, 0))
+            return
+        unknown = set(params) - set(DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown dynamic-mask parameters {sorted(unknown)}")
+        p = {**DEFAULTS, **params}
+        prm = TsdfDynamicParams(float(p["min_free_weight"]), float(p["free_fraction"]), int(p["open_radius"]),
+                                int(p["dilate_radius"]), (ctypes.c_int32 * 4)())
+        _check(self.lib.tslam_tsdf_dynamic_init(self.h, int(pair), int(bool(rect)), ctypes.addressof(prm), int(max_frames)))
+
+    def tsdf_dynamic(self, depth_dev_ptr: int, stride_bytes: int, n_frames: int, first_frame: int = 0,
+                     world_T_cam: np.ndarray | None = None, stream: int = 0) -> None:
+        """The mask and the filtered depth of n depth frames (device u16 mm, ``stride_bytes`` apart)
+        into slots 0.. on the stream (asynchronous), at the host poses world_T_cam [n][4][4] (volume
+        frame) or, with None, at the last batch's tracked device poses of frames first_frame.. ."""
+        poses = None
+        if world_T_cam is not None:
+            poses = np.ascontiguousarray(np.asarray(world_T_cam, dtype=np.float64).reshape(-1, 4, 4))
+        self._dynamic_poses = poses   # stays alive behind the asynchronous call
+        _check(self.lib.tslam_tsdf_dynamic(self.h, ctypes.c_void_p(depth_dev_ptr), int(stride_bytes), int(n_frames),
+                                           int(first_frame), None if poses is None else poses.ctypes.data,
+                                           ctypes.c_void_p(stream)))
+
+    def tsdf_dynamic_buffers(self) -> tuple[dict, dict]:
+        """(device pointers of ``depth`` u16 [max_frames][H][W], ``mask`` u8 [max_frames][H][W] and
+        ``stats`` i32 [max_frames][4]; bytes of one frame's ``depth`` and ``mask``)."""
+        names = ("depth", "mask", "stats")
+        ptrs = [ctypes.c_void_p() for _ in names]
+        nbytes = (ctypes.c_int64 * 2)()
+        _check(self.lib.tslam_tsdf_dynamic_buffers(self.h, *[ctypes.byref(p) for p in ptrs], ctypes.addressof(nbytes)))
+        return {k: int(p.value or 0) for k, p in zip(names, ptrs)}, {"depth": int(nbytes[0]), "mask": int(nbytes[1])}
+
+    def tsdf_dynamic_read(self, frame: int = 0) -> dict:
+        """One slot (synchronises): ``mask`` u8 [H][W] (0 or 1), ``depth`` u16 [H][W] (the looked-up
+        depth, 0 under the mask), ``stats`` i32 [4] (status, valid pixels, candidates, valid pixels
+        under the mask)."""
+        out = {"depth": np.zeros((self.height, self.width), np.uint16), "mask": np.zeros((self.height, self.width), np.uint8),
+               "stats": np.zeros(4, np.int32)}
+        _check(self.lib.tslam_tsdf_dynamic_read(self.h, int(frame), *[out[k].ctypes.data for k in ("depth", "mask", "stats")]))
+        return out
 
     # -- depth registration (thor_slam_amd/depth_register.py) ------------------------------------
     def depth_register_init(self, color_width: int, color_height: int, f_c: float, cxc: float, cyc: float, color_T_rect,

@@ -11,6 +11,7 @@ from __future__ import annotations
 from dataclasses import dataclass
 
 from .dense_align import DEFAULTS as ALIGN_DEFAULTS, check_align_params
+from .dense_dynamic import check_dynamic_params
 from .dense_follow import check_follow_params
 from .dense_loop import check_loop_params
 from .dense_rig import DenseCamerasError
@@ -192,6 +193,17 @@ class HipSlamConfig(SlamConfig):
     dense_loop_capacity: int = 1024
     dense_loop_min_translation_m: float | None = None
     dense_loop_min_rotation_rad: float = 0.005
+    # dynamic objects kept out of the dense map (thor_slam_amd/dense_dynamic.py): depth of pair 0 that
+    # lands in voxels the map has seen empty (weight >= dense_dynamic_min_weight, tsdf >=
+    # dense_dynamic_free_fraction of the truncation distance) is masked, the mask opened by
+    # dense_dynamic_open_px and dilated by dense_dynamic_dilate_px pixels, and the depth is integrated
+    # without the masked pixels.  Needs dense_map and one device; dense_follow is allowed;
+    # dense_cameras, dense_align, dense_loop and colour are refused.
+    dense_dynamic: bool = False
+    dense_dynamic_min_weight: float = 5.0
+    dense_dynamic_free_fraction: float = 0.75
+    dense_dynamic_open_px: int = 1
+    dense_dynamic_dilate_px: int = 2
     # dense stereo depth (thor_slam_amd/stereo_depth.py): on a stereo rig, pair 0's depth image is
     # computed on the device from the rectified images (candidate disparities 0 .. max_disparity - 1)
     # and feeds dense_map as an RGB-D camera's depth does (no colour layer: the images are gray, so
@@ -242,6 +254,11 @@ class HipSlamConfig(SlamConfig):
                 "min_weight": self.mesh_integrator_min_weight, "max_depth": self.tsdf_integrator_max_integration_distance_m,
                 "step_scale": self.dense_view_step_scale, "max_translation": self.dense_align_max_translation_m,
                 "max_rotation": self.dense_align_max_rotation_rad}
+
+    def dense_dynamic_params(self) -> dict:
+        """The rule's parameters (thor_slam_amd/dense_dynamic.py) that ``dense_dynamic`` runs with."""
+        return {"min_free_weight": self.dense_dynamic_min_weight, "free_fraction": self.dense_dynamic_free_fraction,
+                "open_radius": self.dense_dynamic_open_px, "dilate_radius": self.dense_dynamic_dilate_px}
 
     def validate(self) -> None:
         if not 1 <= self.n_levels <= MAX_LEVELS:
@@ -344,6 +361,21 @@ class HipSlamConfig(SlamConfig):
             if self.stereo_depth and self.loop_kf_interval % self.stereo_depth_interval != 0:
                 raise ValueError("dense_loop: stereo_depth_interval must divide loop_kf_interval (the node frames are matched)")
             check_loop_params(self.dense_loop_capacity, self.dense_loop_min_translation_m, self.dense_loop_min_rotation_rad)
+        if self.dense_dynamic:
+            if not self.dense_map:
+                raise ValueError("dense_dynamic needs dense_map=True")
+            if self.devices:
+                raise ValueError("dense_dynamic does not run on a sharded rig (devices)")
+            if self.dense_cameras:
+                raise ValueError("dense_dynamic does not run with dense_cameras (it masks pair 0's depth on pair 0's pose)")
+            if self.dense_align:
+                raise ValueError("dense_dynamic does not run with dense_align: aligned integration of filtered depth is not built")
+            if self.dense_loop:
+                raise ValueError("dense_dynamic does not run with dense_loop: the archive would hold the unfiltered frames")
+            if (self.dense_color and self.rgbd) or self.stereo_color:
+                raise ValueError("dense_dynamic needs dense_color=False and stereo_color=False: the filtered depth is on "
+                                 "the rectified grid, the colour is not")
+            check_dynamic_params(**self.dense_dynamic_params(), max_frames=1)
         if not (self.ba_window == 0 or 2 <= self.ba_window <= 10):
             raise ValueError("ba_window must be 0 (off) or in [2, 10]")
         if self.ba_kf_interval < 1 or self.ba_iters < 1:

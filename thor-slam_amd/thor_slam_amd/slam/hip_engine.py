@@ -487,6 +487,16 @@ class HipSlamEngine(SlamEngine):
         d = self._dense_reader(self._config.dense_align)
         return None if d is None else d.alignment()
 
+    def get_dynamic_mask(self) -> dict | None:
+        """The free-space mask of the newest frame that went through it (``dense_dynamic``; the rule is
+        thor_slam_amd/dense_dynamic.py): ``mask`` u8 [H][W] (1: kept out of the map), ``depth`` u16
+        [H][W] in mm on pair 0's rectified grid (what was integrated: 0 under the mask), ``stats`` i32
+        [4] (status: 0 ok, 1 unused; valid pixels; candidates; valid pixels under the mask) and the
+        frame's ``timestamp``.  None unless ``dense_dynamic`` is on and a frame has gone through.
+        Synchronises."""
+        d = self._dense_reader(self._config.dense_dynamic)
+        return None if d is None else d.dynamic_mask()
+
     def get_dense_map(self) -> dict | None:
         """The TSDF volume (nvblox-shaped): ``tsdf`` / ``weight`` f32 [nz][ny][nx] (metres of
         truncated signed distance; weight 0 = never observed), the voxel grid (``origin``,
