@@ -629,6 +629,11 @@ int tslam_select_mode(tslam_handle* h, int mode, int resident_cap);
  * capacity; N > 0: at most N positions of a window are merged, the rest take the direct path in the
  * same launch. */
 int tslam_match_mode(tslam_handle* h, int mode, int merge_cap);
+/* Test hook for the matcher's grid (results are identical in either layout; added within ABI 21: a
+ * new symbol, nothing else changes).  layout 0 (default): one block matches its 128 queries on the
+ * stereo and on the temporal side, after one query-side setup; 1: one block per side, each with a
+ * setup of its own (the tests' reference). */
+int tslam_match_layout(tslam_handle* h, int layout);
 /* Test hook for the descriptor kernel's keypoint list (results are identical for every value).
  * list_cap 0 (default): the built-in capacity; N > 0: a tile lists at most N of the y-sorted
  * records of its rows at a time and serves the rest in further chunks, as it does by itself where

@@ -4,8 +4,17 @@
 // Bit-exact with oracle.match / oracle.stereo_subpixel / oracle.temporal_subpixel.
 //
 // k_match: the Hamming distances come from the matrix cores.  A block holds 128 y-sorted queries
-// of one level, one 32-query MFMA row tile per wave (temporal blocks first re-deal their queries
-// by x, so each wave holds an x-quartile and its column box admits about half of the trains).
+// of one level, one 32-query MFMA row tile per wave, and matches them on both sides: the setup
+// (the query load round, the deal of the queries to the waves, the slot sort, |q|, the A operand
+// and the wave's column extent) runs once, then one pass per side, temporal first, each with its
+// own early-outs, gate words, train rows, walk, (best, second) reduction, stores and tbest flush;
+// the ring, the reduction rows, the merge array and best / second serve one side after the other.
+// The queries are dealt by x, so each wave holds an x-quartile: its column box admits about half
+// of a temporal window's trains, and on either side it walks the block's rows.  A block that owns
+// the stereo side only (the stereo-only launch of a sharded rig, and the split layout of
+// tslam_match_layout, one side per block, which the tests compare against) keeps its queries in
+// y order and each wave walks its own row band.  Results do not depend on the deal: the query
+// side's best and second are order-free minima, the train side's minimum goes by query index.
 // Each wave walks the train rows its queries can reach in chunks of 64 y-sorted positions,
 // compacts the trains inside its column box into an LDS ring (ballot + mbcnt), and scores every
 // full ring tile of 32 trains with four FP4 block-scaled MFMAs:
@@ -78,7 +87,7 @@ __device__ __forceinline__ void match_body(const BatchCtx& c) {
     TS_BACK_PRIO;
     // per wave: the compacted-train ring during the walk, then the (best, second) reduction
     __shared__ __attribute__((aligned(16))) uint2 s_red[4][32 * TS_MRED_PITCH];
-    __shared__ __attribute__((aligned(16))) uint32_t s_key[2][TS_MQ];  // temporal: (x, thread) sort keys, then the dealt positions
+    __shared__ __attribute__((aligned(16))) uint32_t s_key[2][TS_MQ];  // the deal by x: (x, thread) sort keys, then the dealt positions
     __shared__ __attribute__((aligned(16))) uint32_t s_wk[4][32];   // per wave: query-index sort keys
     // the block's query records and descriptors (one load round), in the ring's LDS: they are dead
     // once every wave has built its A operand (the barrier before the walk)
@@ -86,6 +95,9 @@ __device__ __forceinline__ void match_body(const BatchCtx& c) {
     uint4* const s_qdesc = s_qrec + TS_MQ;
     __shared__ uint32_t s_sq[4][32];      // per wave slot: query keypoint index (~0: empty slot)
     __shared__ uint32_t s_si[4][32];      // ... its block-local index
+    // ... its y << 16 | x, [32 wave + slot], in the deal's sort keys: those are dead after the
+    // barrier that publishes the dealt positions
+    uint32_t* const s_sxy = s_key[0];
     // ... gate word (qy + gy_tol) << 16 | (qx - gx_lo) and |q| (popcount of the descriptor), by
     // [wave][slot & 1][slot >> 1]: lane half h reads its 16 accumulator rows as four 16-byte words
     __shared__ __attribute__((aligned(16))) uint32_t s_sg[4][2][16];
@@ -95,13 +107,15 @@ __device__ __forceinline__ void match_body(const BatchCtx& c) {
     // boxes overlap 2:1), so they meet here (ds_min) and each touched position leaves the CU as
     // one global atomic after the walk.  TS_MTB fills the 40 KB that keep 4 blocks on a CU.
     __shared__ uint32_t s_tb[TS_MTB];
-    // blockIdx.y: the temporal blocks (the heavy ones: a window of rows, not a row band) of every
-    // frame first, then the stereo blocks, so the short stereo blocks fill the launch's tail
-    // (stereo-only launches, match_modes == 1: blockIdx.y = f * P + p, all stereo)
-    const int nfp = c.match_modes == 1 ? 0 : c.n * c.npair;
+    // The sides a block owns (bit 0 stereo, bit 1 temporal).  Fused layout (the default): grid
+    // (total_qtiles, n * npair), blockIdx.y = f * npair + (p - pair0), and the block matches its
+    // tile on every side of c.match_modes.  Split layout (tslam_match_layout, the tests' reference):
+    // one side per block, blockIdx.y the temporal blocks of every frame first, then the stereo
+    // blocks.  Stereo-only launches (match_modes == 1) have one stereo block per tile either way.
+    const int npb = c.n * c.npair;
     const int z = blockIdx.y;
-    const int mode = z < nfp ? 1 : 0;
-    const int fl = z < nfp ? z : z - nfp;     // f * npair + (p - pair0)
+    const int sides = c.match_modes == 1 ? 1 : !c.mp.split ? 3 : z < npb ? 2 : 1;
+    const int fl = z < npb ? z : z - npb;     // f * npair + (p - pair0)
     const int f = div_small(fl, c.npair_rcp);
     const int p = c.pair0 + (fl - f * c.npair);
     const int64_t g = c.g0 + f;
@@ -109,50 +123,44 @@ __device__ __forceinline__ void match_body(const BatchCtx& c) {
     while (l + 1 < c.g.n_levels && (int)blockIdx.x >= c.g.qtile_start[l + 1]) ++l;
     const int tile = blockIdx.x - c.g.qtile_start[l];
     const int q0 = tile * TS_MQ;
-    const size_t mbase = (((size_t)f * c.P + p) * 2 + mode) * c.g.K;
-    // A block with nothing to match writes "no match" for its tile's positions of the level itself
-    // (qbest is not cleared before the launch).  Every such return is block-uniform.
-    auto no_match = [&]() {
-        if ((int)threadIdx.x < TS_MQ && q0 + (int)threadIdx.x < c.g.Kq[l]) c.qbest[mbase + c.g.koff[l] + q0 + threadIdx.x] = 0xFFFFFFFFu;
-        if (CNT && threadIdx.x == 0) atomicAdd(&c.match_cnt[8 * mode + TS_MCNT_EMPTY], 1u);
-    };
-    if ((mode == 1 && g == 0) ||              // no previous frame
-        (mode == 0 && c.rgbd)) {              // RGB-D: depth replaces stereo matching
-        no_match();
-        return;
-    }
-    const int slot = batch_slot(c, f);
-    const int qcam = c.cpp * p;
-    const int tslot = mode == 0 ? slot : prev_slot(c, slot);
-    const int tcam = mode == 0 ? qcam + 1 : qcam;
     const int K = c.g.K;
+    const size_t mbase0 = ((size_t)f * c.P + p) * 2 * K;   // the stereo side's words; temporal at + K
+    const int slot = batch_slot(c, f);
+    const int pslot = prev_slot(c, slot);
+    const int qcam = c.cpp * p;
+    const int row_tol = c.mp.row_tol, dmax = c.mp.max_disp >> l, win = c.mp.window >> l;
     const int qn = c.kcount[((size_t)slot * c.C + qcam) * c.g.n_levels + l];
-    const int tn = c.kcount[((size_t)tslot * c.C + tcam) * c.g.n_levels + l];
-    if (q0 >= qn || tn == 0) {
-        no_match();
-        return;
+    const int tn_s = c.rgbd ? 0 : c.kcount[((size_t)slot * c.C + qcam + 1) * c.g.n_levels + l];
+    const int tn_t = c.kcount[((size_t)pslot * c.C + qcam) * c.g.n_levels + l];
+    // A side with nothing to match writes "no match" for the tile's positions of the level itself
+    // (qbest is not cleared before the launch): no previous frame, RGB-D (depth replaces stereo
+    // matching), a tile past the image's count, no train, or an empty disparity range at this
+    // level.  All of it is block-uniform; a block whose sides all end here returns before the setup.
+    int live = 0;
+#pragma unroll
+    for (int mode = 0; mode < 2; ++mode) {
+        if (!(sides >> mode & 1)) continue;
+        const bool dead = q0 >= qn || (mode == 1 ? g == 0 || tn_t == 0 : c.rgbd || tn_s == 0 || dmax < 1);
+        if (!dead) {
+            live |= 1 << mode;
+        } else if ((int)threadIdx.x < TS_MQ && q0 + (int)threadIdx.x < c.g.Kq[l]) {
+            c.qbest[mbase0 + (size_t)mode * K + c.g.koff[l] + q0 + threadIdx.x] = 0xFFFFFFFFu;
+        }
+        if (CNT && threadIdx.x == 0) atomicAdd(&c.match_cnt[8 * mode + (dead ? TS_MCNT_EMPTY : TS_MCNT_WALKED)], 1u);
     }
-    if (CNT && threadIdx.x == 0) atomicAdd(&c.match_cnt[8 * mode + TS_MCNT_WALKED], 1u);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (!live) return;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int ci = lane & 31, h = lane >> 5;  // MFMA column / row index, lane half (k half)
     const size_t qbase = ((size_t)slot * c.C + qcam) * K;
-    const size_t tbase = ((size_t)tslot * c.C + tcam) * K;
     const uint4* qys = c.ys + qbase + c.g.koff[l];           // y-sorted records of the level
-    const uint4* tys = c.ys + tbase + c.g.koff[l];
-    uint32_t* const tb = c.tbest + mbase + c.g.koff[l];   // the level's train minima, by y-sorted position
     const uint4* qdesc = reinterpret_cast<const uint4*>(c.desc_ys + (qbase + c.g.koff[l]) * 8);
-    const uint4* tdesc = reinterpret_cast<const uint4*>(c.desc_ys + (tbase + c.g.koff[l]) * 8);
-    const uint16_t* trs = c.rowstart + ((size_t)tslot * c.C + tcam) * c.g.rs_total + c.g.rs_off[l];
     const int Hl = c.g.H[l];
-    const int row_tol = c.mp.row_tol, dmax = c.mp.max_disp >> l, win = c.mp.window >> l;
-    // the geometric gate as one box: stereo 1 <= x_q - x_t <= max_disp and |y_q - y_t| <= row_tol;
-    // temporal |x_q - x_t| <= window and |y_q - y_t| <= window
-    const int gx_lo = mode == 0 ? 1 : -win, gx_hi = mode == 0 ? dmax : win, gy_tol = mode == 0 ? row_tol : win;
-    const uint32_t span = (uint32_t)(2 * gy_tol) << 16 | (uint32_t)(gx_hi - gx_lo);
+    const uint32_t mcap = (uint32_t)min(c.mp.merge_cap, TS_MTB);
 
+    // ---- the setup, once per block ----
     // The block's 128 query records and descriptors land in LDS in one round of global loads, so
-    // every later setup step reads LDS; the records are y-sorted, so each wave's train rows (and
-    // the row-start loads for them) are known at once.
+    // every later setup step reads LDS; the records are y-sorted, so the train rows of every side
+    // (and the row-start loads for them) are known at once.
     const int nq = min(TS_MQ, qn - q0);
     {
         const int t = threadIdx.x & (TS_MQ - 1), half = threadIdx.x >> 7;
@@ -161,32 +169,19 @@ __device__ __forceinline__ void match_body(const BatchCtx& c) {
         s_qdesc[2 * t + half] = qdesc[2 * pos + half];
     }
     __syncthreads();
-    // this wave's 32 queries (block-local indices): 32 wave + i (stereo: y order), or the block's
-    // x-ranks 32 wave .. 32 wave + 31 (temporal); active ones come first in either order
+    // this wave's 32 queries (block-local indices): the block's x-ranks 32 wave .. 32 wave + 31
+    // where the block owns the temporal side (either side then walks the block's rows), or
+    // 32 wave + i in y order (a stereo-only block: the wave walks its own row band); active ones
+    // come first in either order
+    const bool dealx = (sides & 2) != 0;
     const bool wave_active = 32 * wave < nq;
-    const int reach = mode == 0 ? row_tol : win;
-    int wt0 = 0, wt1 = 0;
-    {
-        // train rows: the wave's own (stereo) or the block's (temporal: an x-quartile spans them)
-        const int i0 = mode == 1 ? 0 : min(32 * wave, nq - 1), i1 = mode == 1 ? nq - 1 : min(32 * wave + 31, nq - 1);
-        const int wy0 = (int)(s_qrec[i0].x >> 16), wy1 = (int)(s_qrec[i1].x >> 16);
-        if (wave_active) {
-            wt0 = (int)trs[max(0, wy0 - reach)];
-            wt1 = (int)trs[min(Hl - 1, wy1 + reach) + 1];
-        }
-    }
-    // the block's train rows (the union of its waves'; temporal: every wave's own), the base and
-    // extent of the merge array; cleared here, before the barrier that ends the setup
-    const uint32_t mcap = (uint32_t)min(c.mp.merge_cap, TS_MTB);
-    int bt0 = 0, bt1 = 0;
-    if (mcap) {
-        const int by0 = (int)(s_qrec[0].x >> 16), by1 = (int)(s_qrec[nq - 1].x >> 16);
-        bt0 = __builtin_amdgcn_readfirstlane((int)trs[max(0, by0 - reach)]);
-        bt1 = __builtin_amdgcn_readfirstlane((int)trs[min(Hl - 1, by1 + reach) + 1]);
-        for (int i = threadIdx.x; i < min((int)mcap, bt1 - bt0); i += 256) s_tb[i] = 0xFFFFFFFFu;
-    }
+    // rows of the block's queries, and of the wave's: uniform, they index the sides' row starts
+    const int by0 = __builtin_amdgcn_readfirstlane((int)(s_qrec[0].x >> 16));
+    const int by1 = __builtin_amdgcn_readfirstlane((int)(s_qrec[nq - 1].x >> 16));
+    const int wy0 = dealx ? by0 : __builtin_amdgcn_readfirstlane((int)(s_qrec[min(32 * wave, nq - 1)].x >> 16));
+    const int wy1 = dealx ? by1 : __builtin_amdgcn_readfirstlane((int)(s_qrec[min(32 * wave + 31, nq - 1)].x >> 16));
     int bi = 32 * wave + ci;
-    if (mode == 1) {
+    if (dealx) {
         if (threadIdx.x < TS_MQ) {
             const int t = threadIdx.x;
             s_key[0][t] = t < nq ? (s_qrec[t].x & 0xFFFF) << 8 | (uint32_t)t : 0x1000000u | (uint32_t)t;
@@ -235,8 +230,7 @@ __device__ __forceinline__ void match_body(const BatchCtx& c) {
         if (h == 0) {
             s_sq[wave][rank] = active ? qi : 0xFFFFFFFFu;
             s_si[wave][rank] = (uint32_t)bi;
-            // inactive: 0xFFFF halves fail every gate
-            s_sg[wave][rank & 1][rank >> 1] = active ? ((uint32_t)(qy + gy_tol) << 16 | ((uint32_t)(qx - gx_lo) & 0xFFFFu)) : 0xFFFFFFFFu;
+            s_sxy[32 * wave + rank] = (uint32_t)qy << 16 | (uint32_t)qx;   // the sides' gate words come from it
             s_spc[wave][rank & 1][rank >> 1] = (float)pc;
         }
     }
@@ -255,9 +249,6 @@ __device__ __forceinline__ void match_body(const BatchCtx& c) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (gx_hi < gx_lo) wt1 = wt0;   // empty disparity range at this level: nothing is eligible
-    // a train column some query of the wave can reach: qx - tx in [gx_lo, gx_hi] for a wave qx
-    const uint32_t bx0 = (uint32_t)(wx0 - gx_hi), bx_span = (uint32_t)(wx1 - gx_lo - (wx0 - gx_hi));
 
     // A operand (rows = slots): lane (row ci, half h) holds, for MFMA step s, bit s of every nibble
     // of descriptor words 4h .. 4h+3 of the query in slot(ci), as +-1
@@ -272,186 +263,226 @@ __device__ __forceinline__ void match_body(const BatchCtx& c) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) qa[s][j] = 0x22222222u | (((w4[j] >> s) & 0x11111111u) << 3);
     }
-    __syncthreads();   // every wave's A operand is built: s_qrec / s_qdesc become ring space
     // per accumulator register: the slot's |q| (the MFMA's C) and gate word, re-read from LDS per
     // tile (32 VGPRs fewer across the walk: 4 waves per SIMD instead of 3)
     const float4* const spc4 = reinterpret_cast<const float4*>(s_spc[wave][h]);
     const uint4* const sg4 = reinterpret_cast<const uint4*>(s_sg[wave][h]);
-    uint32_t best[16], second[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) best[r] = second[r] = 0xFFFFFFFFu;
 
-    // The walk in rounds: compact the trains inside the wave's column box into the ring (chunks of
-    // 64 y-sorted positions, TS_MCHUNKS chunks' record loads in flight at a time) until it holds
-    // TS_MRING - 64 TS_MCHUNKS or more (every round but a rare last one: all of them), then score
-    // the ring's 32-train tiles, each tile's entries and descriptors loaded one tile ahead (two
-    // tiles per loop trip measured slower: 173 VGPRs, 2 waves/SIMD).
-    // Every load is unconditional (indices clamped into the ring; a padding column only gets the
-    // gate-failing xy) and the train-side minima go back into the ring entries (the flush's global
-    // atomics come after the round's last tile), so the loop body is straight-line code whose
-    // vmcnt waits cover exactly the tile being scored.
-    uint2* ring = s_red[wave];   // {txy, tidx << 16 | position}; after scoring {tmin, ...}
-    auto score = [&](const uint4& d, const uint2& e, uint32_t k, uint32_t n) {
-        const uint32_t w4[4] = {d.x, d.y, d.z, d.w};
-        v16f_t acc;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float4 v = spc4[i];
-            acc[4 * i] = v.x;
-            acc[4 * i + 1] = v.y;
-            acc[4 * i + 2] = v.z;
-            acc[4 * i + 3] = v.w;
+    // ---- the pass of one side: temporal (the heavy one) first ----
+    // The ring, the reduction rows, the merge array and best / second serve one side after the other.
+    bool first = true;
+    for (int mode = 1; mode >= 0; --mode) {
+        if (!(live >> mode & 1)) continue;
+        // the previous side's flush has read the merge array before this side clears it
+        if (!first) __syncthreads();
+        first = false;
+        const size_t mbase = mbase0 + (size_t)mode * K;
+        const int tslot = mode == 0 ? slot : pslot;
+        const int tcam = mode == 0 ? qcam + 1 : qcam;
+        const size_t tbase = ((size_t)tslot * c.C + tcam) * K;
+        const uint4* tys = c.ys + tbase + c.g.koff[l];
+        uint32_t* const tb = c.tbest + mbase + c.g.koff[l];   // the level's train minima, by y-sorted position
+        const uint4* tdesc = reinterpret_cast<const uint4*>(c.desc_ys + (tbase + c.g.koff[l]) * 8);
+        const uint16_t* trs = c.rowstart + ((size_t)tslot * c.C + tcam) * c.g.rs_total + c.g.rs_off[l];
+        // the geometric gate as one box: stereo 1 <= x_q - x_t <= max_disp and |y_q - y_t| <= row_tol;
+        // temporal |x_q - x_t| <= window and |y_q - y_t| <= window
+        const int gx_lo = mode == 0 ? 1 : -win, gx_hi = mode == 0 ? dmax : win, gy_tol = mode == 0 ? row_tol : win;
+        const uint32_t span = (uint32_t)(2 * gy_tol) << 16 | (uint32_t)(gx_hi - gx_lo);
+        // train rows: the block's (the base and extent of the merge array) and the wave's, which are
+        // the block's too where the queries are dealt by x (an x-quartile spans the block's rows)
+        const int bt0 = (int)trs[max(0, by0 - gy_tol)], bt1 = (int)trs[min(Hl - 1, by1 + gy_tol) + 1];
+        int wt0 = 0, wt1 = 0;
+        if (wave_active) {
+            wt0 = dealx ? bt0 : (int)trs[max(0, wy0 - gy_tol)];
+            wt1 = dealx ? bt1 : (int)trs[min(Hl - 1, wy1 + gy_tol) + 1];
         }
+        for (int i = threadIdx.x; i < min((int)mcap, bt1 - bt0); i += 256) s_tb[i] = 0xFFFFFFFFu;
+        // the slots' gate words; inactive: 0xFFFF halves fail every gate
+        if (h == 0) {
+            const uint32_t xy = s_sxy[32 * wave + ci];
+            s_sg[wave][ci & 1][ci >> 1] = s_sq[wave][ci] != 0xFFFFFFFFu
+                ? ((xy >> 16) + (uint32_t)gy_tol) << 16 | ((xy - (uint32_t)gx_lo) & 0xFFFFu) : 0xFFFFFFFFu;
+        }
+        // a train column some query of the wave can reach: qx - tx in [gx_lo, gx_hi] for a wave qx
+        const uint32_t bx0 = (uint32_t)(wx0 - gx_hi), bx_span = (uint32_t)(wx1 - gx_lo - (wx0 - gx_hi));
+        // every wave's A operand is built (s_qrec / s_qdesc become ring space), the merge array is clear
+        __syncthreads();
+        uint32_t best[16], second[16];
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            v8i_t a, b;
+        for (int r = 0; r < 16; ++r) best[r] = second[r] = 0xFFFFFFFFu;
+
+        // The walk in rounds: compact the trains inside the wave's column box into the ring (chunks of
+        // 64 y-sorted positions, TS_MCHUNKS chunks' record loads in flight at a time) until it holds
+        // TS_MRING - 64 TS_MCHUNKS or more (every round but a rare last one: all of them), then score
+        // the ring's 32-train tiles, each tile's entries and descriptors loaded one tile ahead (two
+        // tiles per loop trip measured slower: 173 VGPRs, 2 waves/SIMD).
+        // Every load is unconditional (indices clamped into the ring; a padding column only gets the
+        // gate-failing xy) and the train-side minima go back into the ring entries (the flush's global
+        // atomics come after the round's last tile), so the loop body is straight-line code whose
+        // vmcnt waits cover exactly the tile being scored.
+        uint2* ring = s_red[wave];   // {txy, tidx << 16 | position}; after scoring {tmin, ...}
+        auto score = [&](const uint4& d, const uint2& e, uint32_t k, uint32_t n) {
+            const uint32_t w4[4] = {d.x, d.y, d.z, d.w};
+            v16f_t acc;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                a[j] = (int)qa[s][j];
-                b[j] = (int)(s < 3 ? (w4[j] & (0x11111111u << s)) : ((w4[j] >> 1) & 0x44444444u));
-                a[j + 4] = 0;
-                b[j + 4] = 0;
+            for (int i = 0; i < 4; ++i) {
+                const float4 v = spc4[i];
+                acc[4 * i] = v.x;
+                acc[4 * i + 1] = v.y;
+                acc[4 * i + 2] = v.z;
+                acc[4 * i + 3] = v.w;
             }
-            acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc, 4, 4, 0, 127, 0, s == 0 ? 128 : s == 1 ? 127 : 126);
-            // b stays live past the MFMA, so the destination never lands on it: the compiler does
-            // not keep vdst of the block-scaled MFMA apart from its sources (no early-clobber), and
-            // a build that spilled put vdst over srcA and half of srcC — wrong stereo matches
-            // (DESIGN.md §5).  isa_guard.py checks every build's MFMA operands.
-            asm volatile("" ::"v"(b));
-        }
-        const uint32_t txy = k < n ? e.x : 0x80008000u;   // padding fails every gate
-        const uint32_t tidx = e.y >> 16;
-        uint32_t tmin = 0xFFFFFFFFu;
-        uint32_t qgate[16];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint4 v = sg4[i];
-            qgate[4 * i] = v.x;
-            qgate[4 * i + 1] = v.y;
-            qgate[4 * i + 2] = v.z;
-            qgate[4 * i + 3] = v.w;
-        }
+            for (int s = 0; s < 4; ++s) {
+                v8i_t a, b;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const uint32_t hb = gate_ok(qgate[r], txy, span) ? __float_as_uint(acc[r]) : 0x7F800000u;
-            const uint32_t key = hb | tidx;
-            second[r] = med3_u32(best[r], second[r], key);   // = min(second, max(best, key)): best <= second
-            best[r] = min(best[r], key);
-            tmin = min(tmin, hb | (uint32_t)(2 * r));
-        }
-        tmin |= (uint32_t)h;
-        tmin = min(tmin, (uint32_t)__shfl_xor((int)tmin, 32, 64));
-        if (h == 0 && k < n) ring[k].x = tmin;
-    };
-    for (int jt = wt0; jt < wt1;) {
-        uint32_t n = 0;
-        for (; jt < wt1 && n <= TS_MRING - 64 * TS_MCHUNKS; jt += 64 * TS_MCHUNKS) {
-            uint4 r4[TS_MCHUNKS];
-#pragma unroll
-            for (int u = 0; u < TS_MCHUNKS; ++u) r4[u] = tys[min(jt + 64 * u + lane, wt1 - 1)];
-#pragma unroll
-            for (int u = 0; u < TS_MCHUNKS; ++u) {
-                const int j = jt + 64 * u + lane;
-                const bool inbox = j < wt1 && (uint32_t)((int)(r4[u].x & 0xFFFF) - (int)bx0) <= bx_span;
-                const uint64_t m = __ballot(inbox);
-                if (inbox)
-                    ring[n + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] =
-                        uint2{r4[u].x, r4[u].z << 16 | (uint32_t)j};
-                n += (uint32_t)__popcll(m);
+                for (int j = 0; j < 4; ++j) {
+                    a[j] = (int)qa[s][j];
+                    b[j] = (int)(s < 3 ? (w4[j] & (0x11111111u << s)) : ((w4[j] >> 1) & 0x44444444u));
+                    a[j + 4] = 0;
+                    b[j + 4] = 0;
+                }
+                acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc, 4, 4, 0, 127, 0, s == 0 ? 128 : s == 1 ? 127 : 126);
+                // b stays live past the MFMA, so the destination never lands on it: the compiler does
+                // not keep vdst of the block-scaled MFMA apart from its sources (no early-clobber), and
+                // a build that spilled put vdst over srcA and half of srcC — wrong stereo matches
+                // (DESIGN.md §5).  isa_guard.py checks every build's MFMA operands.
+                asm volatile("" ::"v"(b));
             }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (n > 0) {
-            const uint32_t last = n - 1;
-            uint2 e0 = ring[min((uint32_t)ci, last)];
-            uint4 d0 = tdesc[2 * (int)(e0.y & 0xFFFFu) + h];
-            for (uint32_t k = (uint32_t)ci; k - (uint32_t)ci < n; k += 32u) {
-                const uint2 e1 = ring[min(k + 32u, last)];
-                const uint4 d1 = tdesc[2 * (int)(e1.y & 0xFFFFu) + h];
-                score(d0, e0, k, n);
-                e0 = e1;
-                d0 = d1;
+            const uint32_t txy = k < n ? e.x : 0x80008000u;   // padding fails every gate
+            const uint32_t tidx = e.y >> 16;
+            uint32_t tmin = 0xFFFFFFFFu;
+            uint32_t qgate[16];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const uint4 v = sg4[i];
+                qgate[4 * i] = v.x;
+                qgate[4 * i + 1] = v.y;
+                qgate[4 * i + 2] = v.z;
+                qgate[4 * i + 3] = v.w;
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const uint32_t hb = gate_ok(qgate[r], txy, span) ? __float_as_uint(acc[r]) : 0x7F800000u;
+                const uint32_t key = hb | tidx;
+                second[r] = med3_u32(best[r], second[r], key);   // = min(second, max(best, key)): best <= second
+                best[r] = min(best[r], key);
+                tmin = min(tmin, hb | (uint32_t)(2 * r));
+            }
+            tmin |= (uint32_t)h;
+            tmin = min(tmin, (uint32_t)__shfl_xor((int)tmin, 32, 64));
+            if (h == 0 && k < n) ring[k].x = tmin;
+        };
+        for (int jt = wt0; jt < wt1;) {
+            uint32_t n = 0;
+            for (; jt < wt1 && n <= TS_MRING - 64 * TS_MCHUNKS; jt += 64 * TS_MCHUNKS) {
+                uint4 r4[TS_MCHUNKS];
+#pragma unroll
+                for (int u = 0; u < TS_MCHUNKS; ++u) r4[u] = tys[min(jt + 64 * u + lane, wt1 - 1)];
+#pragma unroll
+                for (int u = 0; u < TS_MCHUNKS; ++u) {
+                    const int j = jt + 64 * u + lane;
+                    const bool inbox = j < wt1 && (uint32_t)((int)(r4[u].x & 0xFFFF) - (int)bx0) <= bx_span;
+                    const uint64_t m = __ballot(inbox);
+                    if (inbox)
+                        ring[n + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] =
+                            uint2{r4[u].x, r4[u].z << 16 | (uint32_t)j};
+                    n += (uint32_t)__popcll(m);
+                }
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            // flush: each train's (distance, query) minimum over the wave's queries, into the block's
-            // merge array or, past its capacity, straight into tbest (both by position)
-            for (uint32_t k = (uint32_t)lane; k < n; k += 64) {
-                const uint2 e = ring[k];
-                const bool hit = e.x < 0x7F800000u;
-                const uint32_t rel = (e.y & 0xFFFFu) - (uint32_t)bt0;
-                if (hit) {
-                    const uint32_t v = key_dist(e.x & ~31u) << 16 | s_sq[wave][e.x & 31u];
-                    if (rel < mcap)
-                        atomicMin(&s_tb[rel], v);
-                    else
-                        atomicMin(&tb[e.y & 0xFFFFu], v);
+            if (n > 0) {
+                const uint32_t last = n - 1;
+                uint2 e0 = ring[min((uint32_t)ci, last)];
+                uint4 d0 = tdesc[2 * (int)(e0.y & 0xFFFFu) + h];
+                for (uint32_t k = (uint32_t)ci; k - (uint32_t)ci < n; k += 32u) {
+                    const uint2 e1 = ring[min(k + 32u, last)];
+                    const uint4 d1 = tdesc[2 * (int)(e1.y & 0xFFFFu) + h];
+                    score(d0, e0, k, n);
+                    e0 = e1;
+                    d0 = d1;
                 }
-                if (CNT) {
-                    const uint32_t nm = (uint32_t)__popcll(__ballot(hit && rel < mcap)), nd = (uint32_t)__popcll(__ballot(hit && rel >= mcap));
-                    if (lane == 0 && nm) atomicAdd(&c.match_cnt[8 * mode + TS_MCNT_MERGED], nm);
-                    if (lane == 0 && nd) atomicAdd(&c.match_cnt[8 * mode + TS_MCNT_DIRECT], nd);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                // flush: each train's (distance, query) minimum over the wave's queries, into the block's
+                // merge array or, past its capacity, straight into tbest (both by position)
+                for (uint32_t k = (uint32_t)lane; k < n; k += 64) {
+                    const uint2 e = ring[k];
+                    const bool hit = e.x < 0x7F800000u;
+                    const uint32_t rel = (e.y & 0xFFFFu) - (uint32_t)bt0;
+                    if (hit) {
+                        const uint32_t v = key_dist(e.x & ~31u) << 16 | s_sq[wave][e.x & 31u];
+                        if (rel < mcap)
+                            atomicMin(&s_tb[rel], v);
+                        else
+                            atomicMin(&tb[e.y & 0xFFFFu], v);
+                    }
+                    if (CNT) {
+                        const uint32_t nm = (uint32_t)__popcll(__ballot(hit && rel < mcap)), nd = (uint32_t)__popcll(__ballot(hit && rel >= mcap));
+                        if (lane == 0 && nm) atomicAdd(&c.match_cnt[8 * mode + TS_MCNT_MERGED], nm);
+                        if (lane == 0 && nd) atomicAdd(&c.match_cnt[8 * mode + TS_MCNT_DIRECT], nd);
+                    }
                 }
             }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the ring is refilled by the next round
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the ring is refilled by the next round
+
+        // per slot: merge the 32 columns' (best, second) — best = min, second = min(s1, s2, max(b1, b2))
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-
-    // per slot: merge the 32 columns' (best, second) — best = min, second = min(s1, s2, max(b1, b2))
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    uint2* red = s_red[wave];
+        uint2* red = s_red[wave];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) red[(2 * r + h) * TS_MRED_PITCH + ci] = uint2{best[r], second[r]};
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    uint32_t b = 0xFFFFFFFFu, s2 = 0xFFFFFFFFu;
+        for (int r = 0; r < 16; ++r) red[(2 * r + h) * TS_MRED_PITCH + ci] = uint2{best[r], second[r]};
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        uint32_t b = 0xFFFFFFFFu, s2 = 0xFFFFFFFFu;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const uint2 v = red[ci * TS_MRED_PITCH + 16 * h + i];
-        s2 = min(min(s2, v.y), max(b, v.x));
-        b = min(b, v.x);
-    }
-    {
-        const uint32_t ob = (uint32_t)__shfl_xor((int)b, 32, 64), os = (uint32_t)__shfl_xor((int)s2, 32, 64);
-        s2 = min(min(s2, os), max(b, ob));
-        b = min(b, ob);
-    }
-    // stored by the query's y-sorted position (the refinement kernels load them beside its record)
-    // An empty slot stands for a position past the image's count: inside the level it gets the "no
-    // match" word (no memset of qbest: every position of a level is some block's to write).
-    const uint32_t qk = s_sq[wave][ci];
-    const int qpos = q0 + (int)s_si[wave][ci];
-    if (h == 0 && qpos < c.g.Kq[l]) {
-        const size_t qp = mbase + c.g.koff[l] + qpos;
-        const bool found = qk != 0xFFFFFFFFu && b < 0x7F800000u;
-        c.qbest[qp] = found ? key_dist(b) << 16 | (b & 0x7FFFu) : 0xFFFFFFFFu;
-        if (qk != 0xFFFFFFFFu) c.qsecond[qp] = s2 < 0x7F800000u ? key_dist(s2) : 256u;
-        // where the best train's tbest word lies (the key carries its keypoint index: the tie-break
-        // orders by index); one gather per wave, so the refinement loads tbest in its second round
-        c.qtpos[qp] = found ? c.ypos[tbase + (b & 0x7FFFu)] : (uint16_t)0;
-    }
-    // the block's merged train minima: one global atomic per position that any wave touched
-    if (mcap) {
-        __syncthreads();
-        const int len = min((int)mcap, bt1 - bt0);
-        uint32_t na = 0;
-        for (int i = threadIdx.x; i < len; i += 256) {
-            const uint32_t v = s_tb[i];
-            if (v != 0xFFFFFFFFu) {
-                atomicMin(&tb[bt0 + i], v);   // a contiguous range of tbest
-                ++na;
-            }
+        for (int i = 0; i < 16; ++i) {
+            const uint2 v = red[ci * TS_MRED_PITCH + 16 * h + i];
+            s2 = min(min(s2, v.y), max(b, v.x));
+            b = min(b, v.x);
         }
-        if (CNT && na) atomicAdd(&c.match_cnt[8 * mode + TS_MCNT_FLUSHED], na);
-    }
+        {
+            const uint32_t ob = (uint32_t)__shfl_xor((int)b, 32, 64), os = (uint32_t)__shfl_xor((int)s2, 32, 64);
+            s2 = min(min(s2, os), max(b, ob));
+            b = min(b, ob);
+        }
+        // stored by the query's y-sorted position (the refinement kernels load them beside its record)
+        // An empty slot stands for a position past the image's count: inside the level it gets the "no
+        // match" word (no memset of qbest: every position of a level is some block's to write).
+        const uint32_t qk = s_sq[wave][ci];
+        const int qpos = q0 + (int)s_si[wave][ci];
+        if (h == 0 && qpos < c.g.Kq[l]) {
+            const size_t qp = mbase + c.g.koff[l] + qpos;
+            const bool found = qk != 0xFFFFFFFFu && b < 0x7F800000u;
+            c.qbest[qp] = found ? key_dist(b) << 16 | (b & 0x7FFFu) : 0xFFFFFFFFu;
+            if (qk != 0xFFFFFFFFu) c.qsecond[qp] = s2 < 0x7F800000u ? key_dist(s2) : 256u;
+            // where the best train's tbest word lies (the key carries its keypoint index: the tie-break
+            // orders by index); one gather per wave, so the refinement loads tbest in its second round
+            c.qtpos[qp] = found ? c.ypos[tbase + (b & 0x7FFFu)] : (uint16_t)0;
+        }
+        // the block's merged train minima: one global atomic per position that any wave touched
+        if (mcap) {
+            __syncthreads();
+            const int len = min((int)mcap, bt1 - bt0);
+            uint32_t na = 0;
+            for (int i = threadIdx.x; i < len; i += 256) {
+                const uint32_t v = s_tb[i];
+                if (v != 0xFFFFFFFFu) {
+                    atomicMin(&tb[bt0 + i], v);   // a contiguous range of tbest
+                    ++na;
+                }
+            }
+            if (CNT && na) atomicAdd(&c.match_cnt[8 * mode + TS_MCNT_FLUSHED], na);
+        }
+    }   // the side
 }
 
 // Sub-pixel offset of a discrete minimum from three integer costs (exact double division).
@@ -916,7 +947,8 @@ int match_blocks_per_cu() {
 // every position of every level it is launched for
 void launch_match(const BatchCtx& c, hipStream_t s) {
     (void)hipMemsetAsync(c.tbest, 0xFF, sizeof(uint32_t) * (size_t)c.n * c.P * 2 * c.g.K, s);
-    dim3 grid(c.g.total_qtiles, c.n * c.npair * (c.match_modes == 1 ? 1 : 2));
+    // one block per tile and frame pair serves both sides; the split layout has one per side
+    dim3 grid(c.g.total_qtiles, c.n * c.npair * (c.match_modes != 1 && c.mp.split ? 2 : 1));
     launch_k_match(c, grid, s);
 }
 

@@ -218,6 +218,7 @@ BatchCtx make_ctx(tslam_handle* h) {
     c.mp.window = h->prm.temporal_window;
     c.mp.refine_split = h->prm.match_refine;
     c.mp.merge_cap = h->match_mode == 1 ? 0 : h->match_cap > 0 ? std::min(h->match_cap, TS_MTB) : TS_MTB;
+    c.mp.split = h->match_split;
     c.match_cnt = h->d_match_cnt;
     c.det_cnt = h->d_det_cnt;
     c.pp.n_hyp = h->prm.ransac_hypotheses;
@@ -888,6 +889,12 @@ int tslam_match_mode(tslam_handle* h, int mode, int merge_cap) {
     if (!h || mode < 0 || mode > 2 || merge_cap < 0) return fail(TSLAM_EINVAL, "bad handle, match mode or capacity");
     h->match_mode = mode;
     h->match_cap = merge_cap;
+    return TSLAM_OK;
+}
+
+int tslam_match_layout(tslam_handle* h, int layout) {
+    if (!h || layout < 0 || layout > 1) return fail(TSLAM_EINVAL, "bad handle or match layout");
+    h->match_split = layout;
     return TSLAM_OK;
 }
 

@@ -106,6 +106,7 @@ struct MatchParams {
     int max_hamming, ratio_pct, row_tol, max_disp, window;
     int refine_split;   // stereo + temporal refinement: 0 one fused kernel (k_refine_pair), 1 the two kernels
     int merge_cap;      // k_match: train positions per block merged in LDS before tbest (0: none; tslam_match_mode)
+    int split;          // k_match: 0 a block matches both sides of its tile, 1 one side per block (tslam_match_layout)
 };
 
 struct PoseParams {

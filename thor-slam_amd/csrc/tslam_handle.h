@@ -122,6 +122,7 @@ struct tslam_handle {
     // tslam_match_mode: k_match's train-side flush (0 auto, 1 direct, 2 merged per block), a cap on
     // the merge array's entries (0: TS_MTB), and the path counters tslam_match_counters switches on
     int match_mode = 0, match_cap = 0;
+    int match_split = 0;   // tslam_match_layout: 1 = one side per k_match block (the tests' reference)
     // tslam_describe_mode: a cap on the positions k_describe lists at a time (0: TS_DT_LIST)
     int dt_list_cap = 0;
     uint32_t* d_match_cnt = nullptr;

@@ -285,6 +285,7 @@ _SIGNATURES = {
     "tslam_ba_defer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "tslam_select_mode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
     "tslam_match_mode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
+    "tslam_match_layout": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "tslam_describe_mode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "tslam_match_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int)]),
     "tslam_detect_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int]),
@@ -466,6 +467,7 @@ RANSAC_MODE = {"auto": 0, "exhaustive": 1, "bounded": 2}   # tslam_params.ransac
 MATCH_REFINE = {"auto": 0, "split": 1}   # tslam_params.match_refine
 SELECT_MODE = {"auto": 0, "generic": 1, "resident": 2}   # tslam_select_mode
 MATCH_MODE = {"auto": 0, "direct": 1, "merged": 2}   # tslam_match_mode
+MATCH_LAYOUT = {"fused": 0, "split": 1}              # tslam_match_layout
 
 
 def make_params(cfg: HipSlamConfig, max_batch: int, n_pairs: int, ransac_splits: int = 0,
@@ -1555,6 +1557,11 @@ class Handle:
         """``tslam_match_mode`` (test hook): k_match's train-side flush, ``auto`` / ``direct`` (every wave's
         own atomics) / ``merged`` (per block in LDS), and a cap on the merged window positions (0: built in)."""
         _check(self.lib.tslam_match_mode(self.h, MATCH_MODE[mode], int(merge_cap)))
+
+    def match_layout(self, layout: str = "fused") -> None:
+        """``tslam_match_layout`` (test hook): ``fused``, a k_match block matches both sides of its
+        tile (default), or ``split``, one block per side (the tests' reference)."""
+        _check(self.lib.tslam_match_layout(self.h, MATCH_LAYOUT[layout]))
 
     def describe_mode(self, list_cap: int = 0) -> None:
         """``tslam_describe_mode`` (test hook): a cap on the y-sorted positions a k_describe tile lists at
