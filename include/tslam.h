@@ -1095,6 +1095,39 @@ int tslam_tsdf_dynamic(tslam_handle* h, const void* depth, int64_t stride_bytes,
 int tslam_tsdf_dynamic_buffers(tslam_handle* h, void** depth, void** mask, void** stats, int64_t* frame_bytes);
 int tslam_tsdf_dynamic_read(tslam_handle* h, int frame, uint16_t* depth, uint8_t* mask, int32_t* stats);
 
+/* Masked objects that come to rest enter the map: the free-space layer (added within ABI 21: three
+ * new symbols and a struct, nothing else changes, and a handle that never calls the init behaves as
+ * before, bit for bit).  Spec: thor_slam_amd/dense_freespace.py.  One uint32 word per voxel,
+ * [nz][ny][nx]: bits 0..15 `run`, the consecutive occupied observations of the voxel (saturating at
+ * 65535); bit 16 `settled`; higher bits 0.  While the layer exists, a pixel is a candidate of
+ * tslam_tsdf_dynamic only if its voxel's word has settled == 0, judged against the layer as the
+ * stream finds it at that call; after the call's mask outputs are written, the layer is updated with
+ * the call's used frames, in frame order, from the call's raw input depth: a voxel whose centre
+ * projects (tslam_tsdf_integrate's steps) to a valid depth d with sdf = d - p_z is occupied when
+ * |sdf| <= band (run += 1; settled once run >= settle_frames), free when sdf > band (run = 0,
+ * settled cleared), and not observed when sdf < -band; band = occupied_band_vox * voxel_size.  A
+ * release therefore takes effect from the next tslam_tsdf_dynamic call.  The layer moves with the
+ * rolling window (entering voxels are 0) and may exist beside the colour layer.
+ *
+ * tslam_tsdf_freespace_init: a new, all-zero layer with these parameters; NULL params frees it.
+ *   TSLAM_ESTATE without a volume or inside a batch; TSLAM_EINVAL unless 1 <= settle_frames <= 65535,
+ *   occupied_band_vox is finite with 0 < occupied_band_vox <= the volume's trunc_vox, and reserved
+ *   is 0.  A refused call changes nothing.  tslam_reset zeroes the layer; tslam_tsdf_init frees it;
+ *   tslam_tsdf_write does not touch it; tslam_tsdf_shift and the follow decision move it.
+ * tslam_tsdf_freespace_read: the words (synchronises).
+ * tslam_tsdf_freespace_write: replaces the words (synchronises); TSLAM_EINVAL if any bit above 16
+ *   is set.  Both: TSLAM_ESTATE without a volume, without the layer or inside a batch. */
+#define TSLAM_FREESPACE_RUN_MASK 0xffffu
+#define TSLAM_FREESPACE_SETTLED 0x10000u
+typedef struct {
+    double occupied_band_vox;   /* |sdf| <= this many voxels counts as occupied: (0, trunc_vox] */
+    int32_t settle_frames;      /* consecutive occupied observations that release a voxel: 1..65535 */
+    int32_t reserved[5];        /* 0 */
+} tslam_tsdf_freespace_params;
+int tslam_tsdf_freespace_init(tslam_handle* h, const tslam_tsdf_freespace_params* params);
+int tslam_tsdf_freespace_read(tslam_handle* h, uint32_t* words);
+int tslam_tsdf_freespace_write(tslam_handle* h, const uint32_t* words);
+
 /* Depth registration: the depth of a pair's rectified left camera forward-warped into a colour
  * camera with a z-buffer, so that a stereo rig with a centre colour camera gets a coloured dense map
  * and depth aligned to that camera (added within ABI 21: eight new symbols and two structs; nothing

@@ -350,9 +350,13 @@ static void tsdf_integrate_posed(const Args& a, double* poses, hipStream_t s, co
     hipLaunchKernelGGL(k_tsdf_integrate<RIG>, dim3((unsigned)((int64_t)nbx * nby * nbz)), dim3(256), 0, s, b, nbx, nby);
 }
 
+void launch_tsdf_poses(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev, int n, double* poses, hipStream_t s) {
+    hipLaunchKernelGGL(k_tsdf_poses, dim3((n + 63) / 64), dim3(64), 0, s, c, pair, f0, host_wTc_dev, n, poses);
+}
+
 void launch_tsdf(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev, const TsdfArgs& a, double* poses,
                  hipStream_t s, const TsdfFollowCall* follow) {
-    hipLaunchKernelGGL(k_tsdf_poses, dim3((a.n + 63) / 64), dim3(64), 0, s, c, pair, f0, host_wTc_dev, a.n, poses);
+    launch_tsdf_poses(c, pair, f0, host_wTc_dev, a.n, poses, s);
     tsdf_integrate_posed(a, poses, s, follow);
 }
 

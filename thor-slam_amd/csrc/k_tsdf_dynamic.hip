@@ -9,7 +9,8 @@
 //                       four rows.  The pose entry and the window record are read with uniform loads;
 //                       the pixel's depth is looked up as k_tsdf_integrate looks it up and written
 //                       to the output image as it is; its point's voxel is gathered once (tsdf,
-//                       weight).  The wave's candidates are one ballot, written as one word by one
+//                       weight, and the free-space layer's word while that layer exists: a
+//                       settled voxel is no candidate, thor_slam_amd/dense_freespace.py).  The wave's candidates are one ballot, written as one word by one
 //                       lane, with the ballot of its valid pixels beside it; bits past the last
 //                       column are 0.  (Counting here, two atomics per wave on a frame's two
 //                       counters, made this kernel 1.03 ms for 64 frames of 640 x 400; the words
@@ -90,8 +91,9 @@ __global__ __launch_bounds__(256) void k_dynamic_classify(TsdfDynamicArgs a, int
                 g2 <= (double)(a.nz - 1)) {
                 const size_t v = ((size_t)(int)g2 * a.ny + (size_t)(int)g1) * a.nx + (size_t)(int)g0;
                 const float w = a.weight[v], t = a.tsdf[v];
-                // 4: seen free, reliably
-                cand = ((double)w >= a.min_free_weight) & ((double)t >= a.thr);
+                const uint32_t fs = a.layer ? a.layer[v] : 0u;   // the free-space word beside them (uniform: null when off)
+                // 4: seen free, reliably, and not released to the map
+                cand = ((double)w >= a.min_free_weight) & ((double)t >= a.thr) & ((fs & FREESPACE_SETTLED) == 0);
             }
         }
     }

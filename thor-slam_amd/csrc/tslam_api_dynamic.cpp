@@ -108,6 +108,7 @@ int tslam_tsdf_dynamic(tslam_handle* h, const void* depth, int64_t stride_bytes,
     a.thr = p.free_fraction * t.trunc;   // once, here
     a.open_radius = p.open_radius;
     a.dilate_radius = p.dilate_radius;
+    a.layer = h->fs_on ? h->d_fs_words : nullptr;   // the free-space layer as the stream finds it
     a.bits = h->d_dyn_bits;
     a.out_depth = h->d_dyn_depth;
     a.out_mask = h->d_dyn_mask;
@@ -115,6 +116,8 @@ int tslam_tsdf_dynamic(tslam_handle* h, const void* depth, int64_t stride_bytes,
     const double* wtc;   // staged on the stream, as tslam_tsdf_render stages its host poses
     if (const int rc = stage_poses(world_T_cam, n_frames, h->d_dyn_wTc, s, &wtc); rc != TSLAM_OK) return rc;
     launch_tsdf_dynamic(make_ctx(h), h->dyn_pair, f0, wtc, a, h->d_dyn_poses, s);
+    // after the mask outputs: the layer sees the call's used frames, in frame order, in the raw depth
+    freespace_update(h, depth, stride_bytes, n_frames, f0, wtc, s);
     HIPCHK(hipGetLastError());
     return TSLAM_OK;
 }

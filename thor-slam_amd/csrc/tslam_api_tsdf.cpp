@@ -58,10 +58,11 @@ void volume_view(const tslam_handle* h, TsdfRenderArgs& a) {
 // -- the rolling window (thor_slam_amd/dense_follow.py) -----------------------------------------
 static size_t align4(size_t n) { return (n + 3) & ~(size_t)3; }
 
-// the record and the move's scratch, on first use and after a larger tslam_tsdf_init
-static int window_alloc(tslam_handle* h) {
+// the record and the move's scratch, on first use, after a larger tslam_tsdf_init and when the
+// free-space layer is added
+int window_alloc(tslam_handle* h) {
     const size_t nv = tsdf_voxels(h);
-    const size_t floats = 2 * align4(nv) + (h->tsdf.col ? align4(nv) + align4(3 * nv) : 0);
+    const size_t floats = 2 * align4(nv) + (h->tsdf.col ? align4(nv) + align4(3 * nv) : 0) + (h->d_fs_words ? align4(nv) : 0);
     int rc = dev_grow(h, (void**)&h->d_tsdf_scratch, sizeof(float) * floats, &h->tsdf_scratch_cap);
     if (rc == TSLAM_OK && !h->d_tsdf_win) {
         rc = dev_alloc(h, (void**)&h->d_tsdf_win, sizeof(TsdfWindow));
@@ -91,6 +92,8 @@ static TsdfLayers window_layers(const tslam_handle* h) {
         add(t.col_w, 1);
         add(t.col, 3);
     }
+    // the free-space words: one more 1-component 4-byte layer, moved as bits (entering voxels: 0)
+    if (h->d_fs_words) add(reinterpret_cast<float*>(h->d_fs_words), 1);
     return l;
 }
 
@@ -139,6 +142,7 @@ int dense_reset(tslam_handle* h) {
             HIPCHK(hipMemset(h->tsdf.col_w, 0, sizeof(float) * nv));
         }
         if (const int rc = archive_reset(h); rc != TSLAM_OK) return rc;
+        if (const int rc = freespace_reset(h); rc != TSLAM_OK) return rc;
     }
     if (h->rnd_on) {   // the render state stays, its images do not
         const size_t n = (size_t)h->rnd_prm.width * h->rnd_prm.height * h->rnd_views;
@@ -185,6 +189,7 @@ int tslam_tsdf_init(tslam_handle* h, const double* origin, const int32_t* dims, 
     h->tsdf_follow_on = false;
     align_off(h);   // the align state belongs to the volume it was made for
     dynamic_off(h);   // and the free-space mask's state
+    freespace_off(h);   // and the free-space layer
     archive_off(h);   // and so does the depth archive
     a.nx = dims[0];
     a.ny = dims[1];
@@ -194,6 +199,7 @@ int tslam_tsdf_init(tslam_handle* h, const double* origin, const int32_t* dims, 
     a.oz = origin[2];
     a.s = voxel_size;
     a.trunc = trunc_vox * voxel_size;
+    h->tsdf_trunc_vox = trunc_vox;
     a.max_dist = max_dist;
     a.max_weight = max_weight;
     h->tsdf_on = true;

@@ -380,9 +380,9 @@ struct TsdfFollow {
 };
 // the layers of a volume as the move sees them: rows of nx * comp floats, ny * nz rows per layer
 struct TsdfLayers {
-    float* vol[4];
-    float* scratch[4];
-    int comp[4];
+    float* vol[5];       // tsdf, weight, colour weight and colour, the free-space words (moved as bits)
+    float* scratch[5];
+    int comp[5];
     int n;
     int nx, ny, nz;
 };
@@ -497,6 +497,7 @@ struct TsdfDynamicArgs {
     const int32_t* map;        // as TsdfArgs::map
     double max_dist;           // the volume's
     double min_free_weight, thr;   // thr = free_fraction * trunc, rounded once on the host
+    const uint32_t* layer;     // the free-space words [nz][ny][nx] (a settled voxel is no candidate), or null
     int open_radius, dilate_radius;
     const double* poses;       // [n][TSDF_POSE]: world_T_cam R rows (9), centre (3), use flag
     uint64_t* bits;            // scratch: per (frame, row, 64 columns) the candidates' word and the valid pixels' word
@@ -507,6 +508,17 @@ struct TsdfDynamicArgs {
 // pair, f0, host_wTc_dev and poses as launch_tsdf_render
 void launch_tsdf_dynamic(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev, const TsdfDynamicArgs& a,
                          double* poses, hipStream_t s);
+// The free-space layer's update (k_tsdf_freespace.hip; thor_slam_amd/dense_freespace.py): the used
+// frames of a (depth, camera, n, stride and volume as for launch_tsdf; its tsdf / weight / colour are
+// not touched) observe every voxel in frame order: occupied within `band` of the surface, free in
+// front of it.  pair, f0, host_wTc_dev and poses (cam_T_world, written here by launch_tsdf_poses) as
+// launch_tsdf.
+#define FREESPACE_RUN_MASK 0xffffu
+#define FREESPACE_SETTLED 0x10000u
+void launch_tsdf_freespace(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev, const TsdfArgs& a, uint32_t* words,
+                           double band, int settle_frames, double* poses, hipStream_t s);
+// launch_tsdf's pose kernel alone (k_tsdf_poses): n entries of the integrator's table
+void launch_tsdf_poses(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev, int n, double* poses, hipStream_t s);
 // launch_tsdf without its pose kernel: the table `poses` [a.n][TSDF_POSE] is already on the stream
 void launch_tsdf_posed(const TsdfArgs& a, double* poses, hipStream_t s, const TsdfFollowCall* follow = nullptr);
 // The depth archive (k_tsdf_move_frames.hip; thor_slam_amd/dense_loop.py): a ring of the depth frames

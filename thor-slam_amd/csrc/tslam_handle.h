@@ -251,6 +251,7 @@ struct tslam_handle {
     bool tsdf_on = false;
     bool tsdf_color = false;          // colour layer (tslam_tsdf_color)
     TsdfArgs tsdf{};
+    double tsdf_trunc_vox = 0.0;      // as tslam_tsdf_init was given it (tsdf.trunc = trunc_vox * s)
     double* d_tsdf_poses = nullptr;   // [TSDF_MAX_FRAMES][TSDF_POSE]
     double* d_tsdf_wTc = nullptr;     // [TSDF_MAX_FRAMES][16] host poses staged
     // the rolling window (tslam_tsdf_follow / _shift): allocated on first use; once the record
@@ -303,6 +304,14 @@ struct tslam_handle {
     uint16_t* d_dyn_depth = nullptr;
     uint8_t* d_dyn_mask = nullptr;
     int32_t* d_dyn_stats = nullptr;   // [dyn_frames][DYNAMIC_STATS]
+    // ---- tslam_api_freespace.cpp ----
+    // the free-space layer (tslam_tsdf_freespace_*): one word per voxel, its parameters (band =
+    // occupied_band_vox * s, formed once at the init) and the update's pose table
+    bool fs_on = false;
+    double fs_band = 0.0;
+    int fs_settle = 0;
+    uint32_t* d_fs_words = nullptr;   // [nz][ny][nx]: run (bits 0..15), settled (bit 16)
+    double* d_fs_poses = nullptr;     // [TSDF_MAX_FRAMES][TSDF_POSE]: cam_T_world of the call's frames
     // ---- tslam_api_stereo.cpp ----
     // dense stereo depth (tslam_stereo_depth_*): parameters, output slots and winner-map scratch
     bool sd_on = false;
@@ -451,6 +460,9 @@ TSLAM_INTERNAL int batch_frames(const tslam_handle* h, const double* host_poses,
 // host poses [n][16] copied onto the stream into `staging`, *staged = staging; device poses
 // (host null): nothing is copied and *staged = null
 TSLAM_INTERNAL int stage_poses(const double* host, int n, double* staging, hipStream_t s, const double** staged);
+// the window's record and the move's scratch for every layer the volume has now: on first use, after
+// a larger tslam_tsdf_init, and when a layer is added while the record exists
+TSLAM_INTERNAL int window_alloc(tslam_handle* h);
 // the window as the device has it once `s` has drained
 TSLAM_INTERNAL int window_read(tslam_handle* h, hipStream_t s, int32_t shift[3], double origin[3]);
 // a pair's rectified left camera; map: the raw camera's undistortion table, null for depth that is
@@ -482,3 +494,11 @@ TSLAM_INTERNAL void align_off(tslam_handle* h);   // the align state belongs to 
 // -- tslam_api_dynamic.cpp -------------------------------------------------------------------------
 TSLAM_INTERNAL void dynamic_off(tslam_handle* h);    // the mask state belongs to the volume it was made for
 TSLAM_INTERNAL int dynamic_reset(tslam_handle* h);   // tslam_reset: the state stays, its images do not
+
+// -- tslam_api_freespace.cpp -----------------------------------------------------------------------
+TSLAM_INTERNAL void freespace_off(tslam_handle* h);    // the layer belongs to the volume it was made for
+TSLAM_INTERNAL int freespace_reset(tslam_handle* h);   // tslam_reset: the layer is zeroed, as the volume is
+// the layer's update with the frames of a tslam_tsdf_dynamic call, on its stream after its outputs
+// (nothing unless the layer exists); host_wTc_dev: that call's staged host poses, or null
+TSLAM_INTERNAL void freespace_update(tslam_handle* h, const void* depth, int64_t stride_bytes, int n_frames, int f0,
+                                     const double* host_wTc_dev, hipStream_t s);

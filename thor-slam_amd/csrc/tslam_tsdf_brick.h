@@ -1,6 +1,6 @@
 // tslam_tsdf_brick.h — what the kernels that walk the volume brick by brick share: the brick's
 // shape and its view test (k_tsdf.hip: integration; k_tsdf_move_frames.hip: archived frames taken
-// out of the volume and put back at a new pose).
+// out of the volume and put back at a new pose; k_tsdf_freespace.hip: the free-space layer's update).
 #pragma once
 
 #include "tslam_common.h"

@@ -171,6 +171,11 @@ class TsdfDynamicParams(ctypes.Structure):
     ]
 
 
+class TsdfFreespaceParams(ctypes.Structure):
+    """tslam_tsdf_freespace_params: the free-space layer's rule (thor_slam_amd/dense_freespace.py)."""
+    _fields_ = [("occupied_band_vox", ctypes.c_double), ("settle_frames", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
+
+
 def camera_desc(cam) -> CameraDesc:
     """A ``CameraConfig`` (intrinsics + world extrinsics) as a ``tslam_camera_desc``."""
     d = CameraDesc()
@@ -384,6 +389,9 @@ _SIGNATURES = {
                                                   ctypes.c_void_p]),
     "tslam_tsdf_dynamic_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p]),
+    "tslam_tsdf_freespace_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "tslam_tsdf_freespace_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "tslam_tsdf_freespace_write": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "tslam_depth_register_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]),
     "tslam_depth_register": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                             ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
@@ -1292,6 +1300,36 @@ class Handle:
                "stats": np.zeros(4, np.int32)}
         _check(self.lib.tslam_tsdf_dynamic_read(self.h, int(frame), *[out[k].ctypes.data for k in ("depth", "mask", "stats")]))
         return out
+
+    # -- the free-space layer (thor_slam_amd/dense_freespace.py) -----------------------------------
+    def tsdf_freespace_init(self, settle_frames: int = 0, occupied_band_vox: float = 1.5, enable: bool = True) -> None:
+        """A new, all-zero layer: a voxel seen occupied (within ``occupied_band_vox`` voxels of a
+        surface) by ``settle_frames`` consecutive frames of ``tsdf_dynamic`` calls is no longer
+        masked; after ``tsdf_init``.  ``enable`` False frees the layer."""
+        if not enable:
+            _check(self.lib.tslam_tsdf_freespace_init(self.h, None))
+            return
+        prm = TsdfFreespaceParams(float(occupied_band_vox), int(settle_frames), (ctypes.c_int32 * 5)())
+        _check(self.lib.tslam_tsdf_freespace_init(self.h, ctypes.addressof(prm)))
+
+    def tsdf_freespace_read(self) -> np.ndarray:
+        """The layer's words u32 [nz][ny][nx] (bits 0..15 ``run``, bit 16 ``settled``); synchronises."""
+        if getattr(self, "_tsdf_dims", None) is None:   # no volume yet: the library says so
+            _check(self.lib.tslam_tsdf_freespace_read(self.h, None))
+        nx, ny, nz = self._tsdf_dims
+        w = np.zeros((nz, ny, nx), dtype=np.uint32)
+        _check(self.lib.tslam_tsdf_freespace_read(self.h, w.ctypes.data))
+        return w
+
+    def tsdf_freespace_write(self, words: np.ndarray) -> None:
+        """Replace the layer's words (u32 [nz][ny][nx], no bit above 16; synchronises)."""
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        if getattr(self, "_tsdf_dims", None) is None:   # no volume yet: the library says so
+            _check(self.lib.tslam_tsdf_freespace_write(self.h, w.ctypes.data))
+        nx, ny, nz = self._tsdf_dims
+        if w.shape != (nz, ny, nx):
+            raise ValueError(f"layer must be {(nz, ny, nx)}")
+        _check(self.lib.tslam_tsdf_freespace_write(self.h, w.ctypes.data))
 
     # -- depth registration (thor_slam_amd/depth_register.py) ------------------------------------
     def depth_register_init(self, color_width: int, color_height: int, f_c: float, cxc: float, cyc: float, color_T_rect,

@@ -25,7 +25,8 @@ written order.  Images and voxels are widened on load.
 * **3. Voxel.**  ``g[a] = floor((p[a] - o[a]) / s)``; the point is *inside* when
   ``0 <= g[a] <= n[a] - 1`` on all three axes, tested in floating point (a NaN is outside);
   ``v = (g2 * ny + g1) * nx + g0``.
-* **4. Candidate**: valid, inside, ``weight[v] >= min_free_weight`` and ``tsdf[v] >= thr``.
+* **4. Candidate**: valid, inside, ``weight[v] >= min_free_weight`` and ``tsdf[v] >= thr``; while
+  the free-space layer exists (thor_slam_amd/dense_freespace.py) also ``settled(layer[v]) == 0``.
 * **5. Clean-up** with squares of side ``2 r + 1``; everything outside the image counts as 0 in every
   step.  ``E`` = erosion of the candidates by ``open_radius``; ``O`` = dilation of ``E`` by
   ``open_radius``; ``M`` = dilation of ``O`` by ``dilate_radius``.  A radius of 0 is the identity.
@@ -36,9 +37,11 @@ written order.  Images and voxels are widened on load.
 
 The frames of a call are all judged against the volume as it stands before any of them is integrated.
 
-Out of scope: per-voxel timers (an object that comes to rest in known free space stays masked; nvblox
-resets such voxels after a run of consecutive occupied observations), TSDF decay, colour, rigs,
-aligned and archived integration, sharded engines, connected-component size filters.
+An object that comes to rest in known free space is released to the map by the free-space layer
+(``dense_freespace.py``; opt-in): without it the rule has no memory and such an object stays masked.
+
+Out of scope: TSDF decay, colour, rigs, aligned and archived integration, sharded engines,
+connected-component size filters.
 """
 
 from __future__ import annotations
@@ -83,8 +86,9 @@ def lookup(depth_mm, cam, undistort=None) -> np.ndarray:
     return d[np.clip((mp[..., 1] + 16) >> 5, 0, H - 1), np.clip((mp[..., 0] + 16) >> 5, 0, W - 1)]
 
 
-def candidates(tsdf, weight, origin, s, cam, mm, T, max_dist, min_free_weight, thr):
-    """Steps 1-4 on the looked-up image: (valid [H][W], candidate [H][W]), booleans."""
+def candidates(tsdf, weight, origin, s, cam, mm, T, max_dist, min_free_weight, thr, layer=None):
+    """Steps 1-4 on the looked-up image: (valid [H][W], candidate [H][W]), booleans.  ``layer``: the
+    free-space words u32 [nz][ny][nx] (bit 16: settled), or None."""
     W, H, fx, fy, cx, cy = int(cam[0]), int(cam[1]), *[float(v) for v in cam[2:]]
     nz, ny, nx = tsdf.shape
     s = float(s)
@@ -105,7 +109,10 @@ def candidates(tsdf, weight, origin, s, cam, mm, T, max_dist, min_free_weight, t
     v = (g[2] * ny + g[1]) * nx + g[0]
     w = weight.reshape(-1)[v].astype(np.float64)
     t = tsdf.reshape(-1)[v].astype(np.float64)
-    return valid, valid & inside & (w >= float(min_free_weight)) & (t >= float(thr))
+    cand = valid & inside & (w >= float(min_free_weight)) & (t >= float(thr))
+    if layer is not None:
+        cand &= (np.asarray(layer, dtype=np.uint32).reshape(-1)[v] & np.uint32(0x10000)) == 0
+    return valid, cand
 
 
 def _window_counts(b: np.ndarray, r: int) -> np.ndarray:
@@ -132,7 +139,7 @@ def clean(cand: np.ndarray, open_radius: int, dilate_radius: int) -> np.ndarray:
 
 
 def dynamic_frame(tsdf, weight, origin, s, trunc, cam, depth_mm, world_T_cam, max_dist=10.0, undistort=None,
-                  **params) -> dict:
+                  layer=None, **params) -> dict:
     """One frame: ``mask`` u8 [H][W], ``depth`` u16 [H][W], ``stats`` i32 [4]; for the tests and
     measurements also ``valid`` and ``candidates`` (booleans [H][W])."""
     prm = {**DEFAULTS, **params}
@@ -147,7 +154,7 @@ def dynamic_frame(tsdf, weight, origin, s, trunc, cam, depth_mm, world_T_cam, ma
         return {"mask": none.astype(np.uint8), "depth": mm, "stats": np.array([UNUSED, 0, 0, 0], np.int32),
                 "valid": none, "candidates": none}
     thr = float(prm["free_fraction"]) * float(trunc)
-    valid, cand = candidates(tsdf, weight, origin, s, cam, mm, T, max_dist, prm["min_free_weight"], thr)
+    valid, cand = candidates(tsdf, weight, origin, s, cam, mm, T, max_dist, prm["min_free_weight"], thr, layer)
     M = clean(cand, prm["open_radius"], prm["dilate_radius"])
     return {"mask": M.astype(np.uint8), "depth": np.where(M, 0, mm).astype(np.uint16),
             "stats": np.array([OK, valid.sum(), cand.sum(), (valid & M).sum()], np.int32), "valid": valid, "candidates": cand}

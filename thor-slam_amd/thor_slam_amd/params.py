@@ -12,6 +12,7 @@ from dataclasses import dataclass
 
 from .dense_align import DEFAULTS as ALIGN_DEFAULTS, check_align_params
 from .dense_dynamic import check_dynamic_params
+from .dense_freespace import check_freespace_params
 from .dense_follow import check_follow_params
 from .dense_loop import check_loop_params
 from .dense_rig import DenseCamerasError
@@ -204,6 +205,12 @@ class HipSlamConfig(SlamConfig):
     dense_dynamic_free_fraction: float = 0.75
     dense_dynamic_open_px: int = 1
     dense_dynamic_dilate_px: int = 2
+    # masked objects that come to rest enter the map (thor_slam_amd/dense_freespace.py): a voxel that
+    # dense_dynamic_settle_frames consecutive frames saw within dense_dynamic_band_vox voxels of a
+    # surface is no longer masked, from the next batch on; a frame that sees it free again takes the
+    # release back.  0 = off (a masked object stays masked for ever).  Needs dense_dynamic.
+    dense_dynamic_settle_frames: int = 0
+    dense_dynamic_band_vox: float = 1.5
     # dense stereo depth (thor_slam_amd/stereo_depth.py): on a stereo rig, pair 0's depth image is
     # computed on the device from the rectified images (candidate disparities 0 .. max_disparity - 1)
     # and feeds dense_map as an RGB-D camera's depth does (no colour layer: the images are gray, so
@@ -376,6 +383,13 @@ class HipSlamConfig(SlamConfig):
                 raise ValueError("dense_dynamic needs dense_color=False and stereo_color=False: the filtered depth is on "
                                  "the rectified grid, the colour is not")
             check_dynamic_params(**self.dense_dynamic_params(), max_frames=1)
+        if isinstance(self.dense_dynamic_settle_frames, bool) or not isinstance(self.dense_dynamic_settle_frames, int):
+            raise ValueError("dense_dynamic_settle_frames must be an integer (0 = off)")
+        if self.dense_dynamic_settle_frames != 0:
+            if not self.dense_dynamic:
+                raise ValueError("dense_dynamic_settle_frames needs dense_dynamic=True")
+            check_freespace_params(self.dense_dynamic_settle_frames, self.dense_dynamic_band_vox,
+                                   self.tsdf_integrator_truncation_distance_vox)
         if not (self.ba_window == 0 or 2 <= self.ba_window <= 10):
             raise ValueError("ba_window must be 0 (off) or in [2, 10]")
         if self.ba_kf_interval < 1 or self.ba_iters < 1:

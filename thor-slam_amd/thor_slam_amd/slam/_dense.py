@@ -26,6 +26,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from ..dense_freespace import split
 from ..dense_render import check_render_params, scaled_intrinsics, view_in_volume
 from ..depth_register import DEFAULT_MAX_SPLAT, check_register_params, color_camera, compose_color_T_rect
 
@@ -103,6 +104,8 @@ class DenseMap:
             h.tsdf_archive_init(cfg.dense_loop_capacity, interval=cfg.loop_kf_interval, pair=0, rect=bool(cfg.stereo_depth))
         if cfg.dense_dynamic:   # depth in known free space is kept out (thor_slam_amd/dense_dynamic.py)
             h.tsdf_dynamic_init(pair=0, rect=bool(cfg.stereo_depth), max_frames=cfg.batch_size, **cfg.dense_dynamic_params())
+            if cfg.dense_dynamic_settle_frames:   # masked objects that come to rest are released (thor_slam_amd/dense_freespace.py)
+                h.tsdf_freespace_init(settle_frames=cfg.dense_dynamic_settle_frames, occupied_band_vox=cfg.dense_dynamic_band_vox)
         if cfg.stereo_depth:   # a stereo rig: the depth comes from the dense matcher (slots per camera)
             h.stereo_depth_init(max_frames=cfg.batch_size * max(1, len(self.dense)),
                                 uniqueness=cfg.stereo_depth_uniqueness, lr_tol=cfg.stereo_depth_lr_tol)
@@ -300,6 +303,12 @@ class DenseMap:
             return None
         slot, stamp = self.dyn_last
         return {**self.h.tsdf_dynamic_read(slot), "timestamp": stamp}
+
+    def freespace(self, world_T_volume: np.ndarray) -> dict:
+        h = self.h
+        run, settled = split(h.tsdf_freespace_read())
+        shift, origin = h.tsdf_window()
+        return {"run": run, "settled": settled, "origin": origin, "window_shift": shift, "world_T_volume": world_T_volume}
 
     def depth_image(self, pair: int) -> tuple | None:
         if pair not in self.sd_last:

@@ -497,6 +497,16 @@ class HipSlamEngine(SlamEngine):
         d = self._dense_reader(self._config.dense_dynamic)
         return None if d is None else d.dynamic_mask()
 
+    def get_freespace(self) -> dict | None:
+        """The free-space layer (``dense_dynamic_settle_frames``; the rule is
+        thor_slam_amd/dense_freespace.py) on the volume's grid: ``run`` u16 [nz][ny][nx] (consecutive
+        frames that saw a surface in the voxel) and ``settled`` bool [nz][ny][nx] (the voxel is no
+        longer masked: what comes to rest there enters the map from the next batch on), with
+        ``origin``, ``window_shift`` and ``world_T_volume`` as ``get_dense_map`` gives them.  None
+        unless the option is on.  Synchronises."""
+        d = self._dense_reader(self._config.dense_dynamic and self._config.dense_dynamic_settle_frames > 0)
+        return None if d is None else d.freespace(self._world_T_volume)
+
     def get_dense_map(self) -> dict | None:
         """The TSDF volume (nvblox-shaped): ``tsdf`` / ``weight`` f32 [nz][ny][nx] (metres of
         truncated signed distance; weight 0 = never observed), the voxel grid (``origin``,
