@@ -950,6 +950,41 @@ int tslam_tsdf_follow(tslam_handle* h, const tslam_tsdf_follow_params* params);
 int tslam_tsdf_shift(tslam_handle* h, const int32_t* delta, void* stream);
 int tslam_tsdf_window(tslam_handle* h, int32_t* shift, double* origin);
 
+/* The brick store behind the rolling window (added within ABI 21: three new symbols; nothing else
+ * changes, and a handle that never calls tslam_tsdf_store_init behaves as before).  Spec:
+ * thor_slam_amd/dense_store.py; tests/ref_tsdf_store.py restates it.
+ *
+ * With the store on, a move of the window (the follow decision of an integrate call, or
+ * tslam_tsdf_shift) keeps what it used to drop.  Window voxel (i, j, k) under the cumulative shift
+ * is absolute voxel a = (i, j, k) + shift, in store brick b = floor(a / 8) per axis (8 x 8 x 8
+ * voxels; brick (0, 0, 0) starts at the unshifted origin) at local index a - 8 b.  Before the move
+ * every voxel that has no place in the moved window and has a non-zero 32-bit word in any layer
+ * (tsdf, weight, colour weight, colour, free-space words) is written to the store; after it every
+ * voxel the move had no source for takes its words from the store, where they are zeroed.  A voxel
+ * lives in the window or in the store, never in both.  All of it runs on the call's stream, on the
+ * device, without a host synchronise.  The pool holds capacity_bricks bricks and never frees one; a
+ * leaving voxel whose brick cannot be allocated, or whose brick coordinate is outside
+ * [-2^20, 2^20) on an axis, is dropped and counted.
+ *
+ * tslam_tsdf_store_init: a new, empty store of capacity_bricks bricks, sized for the layers the
+ *   volume has now (so after tslam_tsdf_color and tslam_tsdf_freespace_init); 0 frees it.
+ *   TSLAM_ESTATE without a volume, inside a batch, or while the depth archive is on (which then
+ *   refuses tslam_tsdf_archive_init in turn); TSLAM_EINVAL for capacity_bricks < 0 or above 2^30.
+ *   While the store is on, tslam_tsdf_freespace_init refuses to add or free the layer
+ *   (TSLAM_ESTATE).  tslam_tsdf_init and tslam_reset empty the store and leave it on;
+ *   tslam_tsdf_init, which frees the free-space layer, sizes the bricks for the layers that remain.
+ *   tslam_tsdf_follow does not touch it; tslam_tsdf_write / _write_color act on the window only.
+ * tslam_tsdf_store_stats: out8 = capacity, bricks allocated, bricks that hold a voxel, voxels
+ *   stored, voxels dropped, moves (calls whose delta was not zero), words per voxel, 0.  Synchronises.
+ * tslam_tsdf_store_read: the bricks that hold a voxel, in ascending (bz, by, bx): *n_bricks, and
+ *   when the pointers are given brick_xyz [n][3] and words [n][C][8][8][8] (z, y, x; C = words per
+ *   voxel, components in the layers' order above, the colour's three as R, G, B).  Both pointers
+ *   NULL: the count only.  TSLAM_EINVAL when *n_bricks > max_bricks.  Synchronises.
+ * Both readers: TSLAM_ESTATE without a volume, without a store, or inside a batch. */
+int tslam_tsdf_store_init(tslam_handle* h, int64_t capacity_bricks);
+int tslam_tsdf_store_stats(tslam_handle* h, int64_t* out8);
+int tslam_tsdf_store_read(tslam_handle* h, int64_t max_bricks, int32_t* brick_xyz, uint32_t* words, int64_t* n_bricks);
+
 /* The dense map seen from a pose: TSDF ray casting (added within ABI 21: four new symbols and a
  * struct; nothing else changes, and a handle that calls none of them behaves as before).  Spec:
  * thor_slam_amd/dense_render.py.  For every pixel of an undistorted pinhole camera at world_T_cam

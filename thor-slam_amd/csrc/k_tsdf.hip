@@ -32,7 +32,8 @@
 //                     the new cumulative shift, into the handle's TsdfWindow record;
 //   k_tsdf_shift      the same two fields from a caller's delta;
 //   k_tsdf_move       every layer of the volume moved by delta into the scratch, and (a second
-//                     launch) copied back; both return at once when delta is zero;
+//                     launch) copied back; both return at once when delta is zero; with the brick
+//                     store on, k_tsdf_store.hip's two kernels run before and after them;
 //   k_tsdf_integrate  with TsdfArgs::win set, the volume's corner is o + s * (double)shift.
 #include <algorithm>
 #include <type_traits>
@@ -323,11 +324,14 @@ void launch_tsdf_shift(TsdfWindow* win, int dx, int dy, int dz, hipStream_t s) {
 
 // a bounded grid: a call that does not move costs two launches of at most TSDF_MOVE_BLOCKS blocks
 #define TSDF_MOVE_BLOCKS 2048
-void launch_tsdf_move(const TsdfLayers& l, const TsdfWindow* win, hipStream_t s) {
+// with the brick store (k_tsdf_store.hip): what leaves goes out before the move, what enters comes in after it
+void launch_tsdf_move(const TsdfLayers& l, const TsdfWindow* win, hipStream_t s, const TsdfStore* store) {
     const int64_t rows = (int64_t)l.ny * l.nz;
     const unsigned blocks = (unsigned)std::min<int64_t>((rows + 3) / 4, TSDF_MOVE_BLOCKS);
+    if (store) launch_tsdf_store_out(l, win, *store, s);
     hipLaunchKernelGGL(k_tsdf_move<false>, dim3(blocks), dim3(256), 0, s, l, win);
     hipLaunchKernelGGL(k_tsdf_move<true>, dim3(blocks), dim3(256), 0, s, l, win);
+    if (store) launch_tsdf_store_in(l, win, *store, s);
 }
 
 // The table `poses` [a.n][TSDF_POSE] is on the stream: the window's decision and move when the call
@@ -336,7 +340,7 @@ template <typename Args>
 static void tsdf_integrate_posed(const Args& a, double* poses, hipStream_t s, const TsdfFollowCall* follow) {
     if (follow) {
         launch_tsdf_follow(poses, a.n, a, follow->f, follow->win, s);
-        launch_tsdf_move(follow->l, follow->win, s);
+        launch_tsdf_move(follow->l, follow->win, s, follow->store);
     }
     Args b = a;
     b.poses = poses;

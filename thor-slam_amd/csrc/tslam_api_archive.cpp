@@ -38,6 +38,7 @@ int tslam_tsdf_archive_init(tslam_handle* h, int pair, int rect, int capacity, i
     if (const int rc = dense_open(h, "tslam_tsdf_archive_init"); rc != TSLAM_OK) return rc;
     if (h->tsdf_color) return fail(TSLAM_ESTATE, "the depth archive does not move the colour layer (tslam_tsdf_color)");
     if (h->tsdf_follow_on) return fail(TSLAM_ESTATE, "the depth archive does not follow the window (tslam_tsdf_follow)");
+    if (h->store_on) return fail(TSLAM_ESTATE, "the depth archive does not run with the brick store (tslam_tsdf_store_init)");
     if (capacity < 1 || interval < 1) return fail(TSLAM_EINVAL, "capacity and interval must be >= 1");
     if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
     h->arc_on = false;

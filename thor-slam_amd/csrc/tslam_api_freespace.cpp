@@ -38,6 +38,9 @@ extern "C" {
 int tslam_tsdf_freespace_init(tslam_handle* h, const tslam_tsdf_freespace_params* params) {
     if (!h) return fail(TSLAM_EINVAL, "null handle");
     if (const int rc = dense_open(h, "tslam_tsdf_freespace_init"); rc != TSLAM_OK) return rc;
+    // the brick store's bricks are sized for the layers it found: the layer is neither added nor freed under it
+    if (h->store_on && (params != nullptr) != h->fs_on)
+        return fail(TSLAM_ESTATE, "the free-space layer cannot be added or freed while the brick store is on (tslam_tsdf_store_init(0) first)");
     if (!params) {   // off: the layer goes back (the move's scratch keeps its size)
         if (const int rc = dense_quiesce(h); rc != TSLAM_OK) return rc;
         freespace_off(h);

@@ -72,7 +72,7 @@ int window_alloc(tslam_handle* h) {
     return rc;
 }
 
-static TsdfLayers window_layers(const tslam_handle* h) {
+TsdfLayers window_layers(const tslam_handle* h) {
     const TsdfArgs& t = h->tsdf;
     const size_t nv = tsdf_voxels(h);
     TsdfLayers l{};
@@ -127,7 +127,7 @@ TsdfArgs integrate_args(const tslam_handle* h, const PairCamera& k, bool color_g
 
 // following: the call's decision and move between chunk 0's poses and its integration
 TsdfFollowCall follow_call(const tslam_handle* h) {
-    return {h->tsdf_follow, h->tsdf_follow_on ? window_layers(h) : TsdfLayers{}, h->d_tsdf_win};
+    return {h->tsdf_follow, h->tsdf_follow_on ? window_layers(h) : TsdfLayers{}, h->d_tsdf_win, store_of(h)};
 }
 
 // tslam_reset: the volume belongs to the session (the stereo depth slots do not: they stay)
@@ -143,6 +143,7 @@ int dense_reset(tslam_handle* h) {
         }
         if (const int rc = archive_reset(h); rc != TSLAM_OK) return rc;
         if (const int rc = freespace_reset(h); rc != TSLAM_OK) return rc;
+        if (const int rc = store_clear(h); rc != TSLAM_OK) return rc;   // the brick store is empty too
     }
     if (h->rnd_on) {   // the render state stays, its images do not
         const size_t n = (size_t)h->rnd_prm.width * h->rnd_prm.height * h->rnd_views;
@@ -205,7 +206,7 @@ int tslam_tsdf_init(tslam_handle* h, const double* origin, const int32_t* dims, 
     h->tsdf_on = true;
     h->esdf_valid = false;   // outputs of the previous volume are gone
     h->mesh_n = 0;
-    return TSLAM_OK;
+    return store_clear(h);   // a new volume: an empty brick store (it stays on)
 }
 
 // its own order of refusals: the depth and the stride before the batch.  color_stride 0: the colour
@@ -269,7 +270,7 @@ int tslam_tsdf_shift(tslam_handle* h, const int32_t* delta, void* stream) {
     if (const int rc = window_alloc(h); rc != TSLAM_OK) return rc;
     hipStream_t s = call_stream(h, stream);
     launch_tsdf_shift(h->d_tsdf_win, delta[0], delta[1], delta[2], s);
-    launch_tsdf_move(window_layers(h), h->d_tsdf_win, s);
+    launch_tsdf_move(window_layers(h), h->d_tsdf_win, s, store_of(h));
     HIPCHK(hipGetLastError());
     h->esdf_valid = false;
     return TSLAM_OK;

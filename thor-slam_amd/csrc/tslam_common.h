@@ -387,15 +387,39 @@ struct TsdfLayers {
     int nx, ny, nz;
 };
 // follow: the decision of an integrate call from the pose table of its first chunk (n entries);
-// shift: the same two fields from a caller's delta; move: the volume through the scratch and back
+// shift: the same two fields from a caller's delta
 void launch_tsdf_follow(const double* poses, int n, const TsdfArgs& a, const TsdfFollow& f, TsdfWindow* win, hipStream_t s);
 void launch_tsdf_shift(TsdfWindow* win, int dx, int dy, int dz, hipStream_t s);
-void launch_tsdf_move(const TsdfLayers& l, const TsdfWindow* win, hipStream_t s);
+// The brick store (thor_slam_amd/dense_store.py; k_tsdf_store.hip): what leaves the window goes
+// into a pool of 8 x 8 x 8 bricks behind a hash table of absolute brick coordinates, what enters
+// comes back from it.  All of it lives on the device; the host only keeps the pointers.
+struct TsdfStoreCounters {
+    unsigned long long dropped;   // leaving non-zero voxels that found no brick
+    unsigned long long moves;     // moves (delta != 0) the store has seen
+    int32_t bricks;               // slots handed out (never above capacity once a kernel has ended)
+    int32_t pad;
+};
+struct TsdfStore {
+    unsigned long long* keys;     // [cells] tslam_tsdf_store.h's keys, 0 = empty
+    int32_t* vals;                // [cells] the key's slot
+    int32_t* occ;                 // [capacity] voxels the slot's brick holds
+    uint32_t* pool;               // [capacity] bricks: per layer [8][8][8][comp] words
+    TsdfStoreCounters* ctr;
+    int32_t capacity;
+    uint32_t mask;                // cells - 1
+    int32_t wpv;                  // words per voxel the pool's bricks were sized for
+};
+// move: the volume through the scratch and back; with a store, k_tsdf_store_out before and
+// k_tsdf_store_in after the two launches
+void launch_tsdf_move(const TsdfLayers& l, const TsdfWindow* win, hipStream_t s, const TsdfStore* store = nullptr);
+void launch_tsdf_store_out(const TsdfLayers& l, const TsdfWindow* win, const TsdfStore& st, hipStream_t s);
+void launch_tsdf_store_in(const TsdfLayers& l, const TsdfWindow* win, const TsdfStore& st, hipStream_t s);
 // what a call's first chunk does between its poses and its integration when the window follows
 struct TsdfFollowCall {
     TsdfFollow f;
     TsdfLayers l;
     TsdfWindow* win;
+    const TsdfStore* store = nullptr;   // the brick store, when it is on
 };
 void launch_tsdf(const BatchCtx& c, int pair, int f0, const double* host_wTc_dev, const TsdfArgs& a, double* poses,
                  hipStream_t s, const TsdfFollowCall* follow = nullptr);

@@ -261,6 +261,12 @@ struct tslam_handle {
     TsdfWindow* d_tsdf_win = nullptr; // {shift, delta}, written on the device
     float* d_tsdf_scratch = nullptr;  // the move's copy of every layer (each layer's base a multiple of 4 floats)
     size_t tsdf_scratch_cap = 0;
+    // ---- tslam_api_store.cpp ----
+    // the brick store behind the window (tslam_tsdf_store_*): table, pool and counters on the device
+    bool store_on = false;
+    TsdfStore store{};
+    int64_t store_cells = 0;
+    size_t store_pool_bytes = 0;      // as allocated (for the layers tslam_tsdf_store_init found)
     // ---- tslam_api_render.cpp ----
     // the volume seen from a pose (tslam_tsdf_render_*): parameters, the camera's ray-length table,
     // the call's pose table and staged host poses, and the images [rnd_views][H][W] of every
@@ -479,6 +485,13 @@ TSLAM_INTERNAL TsdfArgs integrate_args(const tslam_handle* h, const PairCamera& 
 TSLAM_INTERNAL TsdfFollowCall follow_call(const tslam_handle* h);
 // the fields of a that describe the volume: tsdf, weight, dims, origin, s, win (the colour layer is the caller's)
 TSLAM_INTERNAL void volume_view(const tslam_handle* h, TsdfRenderArgs& a);
+
+// the layers of the volume as the move and the brick store see them (the scratch must exist)
+TSLAM_INTERNAL TsdfLayers window_layers(const tslam_handle* h);
+
+// -- tslam_api_store.cpp ---------------------------------------------------------------------------
+TSLAM_INTERNAL int store_clear(tslam_handle* h);   // tslam_tsdf_init, tslam_reset: the store is empty, sized for the layers of now
+static inline const TsdfStore* store_of(const tslam_handle* h) { return h->store_on ? &h->store : nullptr; }
 
 // -- tslam_api_archive.cpp ------------------------------------------------------------------------
 TSLAM_INTERNAL int archive_reset(tslam_handle* h);     // tslam_reset: the ring is empty, the state stays

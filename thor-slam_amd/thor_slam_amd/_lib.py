@@ -416,6 +416,10 @@ _SIGNATURES = {
                                                ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                                ctypes.POINTER(ctypes.c_int64)]),
     "tslam_tsdf_archive_read_depth": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "tslam_tsdf_store_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
+    "tslam_tsdf_store_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "tslam_tsdf_store_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p]),
 }
 
 
@@ -1144,6 +1148,31 @@ class Handle:
         o = np.zeros(3, dtype=np.float64)
         _check(self.lib.tslam_tsdf_window(self.h, sh.ctypes.data, o.ctypes.data))
         return sh, o
+
+    # -- the brick store behind the window (thor_slam_amd/dense_store.py) --------------------------
+    def tsdf_store_init(self, capacity_bricks: int) -> None:
+        """A new, empty store of ``capacity_bricks`` 8 x 8 x 8 bricks for what leaves the window, sized
+        for the layers the volume has now (after ``tsdf_color`` / ``tsdf_freespace_init``); 0 frees it."""
+        _check(self.lib.tslam_tsdf_store_init(self.h, int(capacity_bricks)))
+
+    def tsdf_store_stats(self) -> dict:
+        """The store's counters (synchronises)."""
+        out = np.zeros(8, dtype=np.int64)
+        _check(self.lib.tslam_tsdf_store_stats(self.h, out.ctypes.data))
+        keys = ("capacity", "bricks_allocated", "bricks", "voxels_stored", "voxels_dropped", "moves", "words_per_voxel")
+        return {k: int(v) for k, v in zip(keys, out)}
+
+    def tsdf_store_read(self) -> tuple[np.ndarray, np.ndarray]:
+        """(bricks i32 [n][3] (bx, by, bz), words u32 [n][C][8][8][8]) of the bricks that hold a voxel,
+        in ascending (bz, by, bx); C and the components' order as the move's layers (synchronises)."""
+        n = ctypes.c_int64(0)
+        _check(self.lib.tslam_tsdf_store_read(self.h, 0, None, None, ctypes.addressof(n)))
+        c = self.tsdf_store_stats()["words_per_voxel"]
+        xyz = np.zeros((n.value, 3), dtype=np.int32)
+        words = np.zeros((n.value, c, 8, 8, 8), dtype=np.uint32)
+        if n.value:
+            _check(self.lib.tslam_tsdf_store_read(self.h, n.value, xyz.ctypes.data, words.ctypes.data, ctypes.addressof(n)))
+        return xyz, words
 
     # -- the volume seen from a pose (thor_slam_amd/dense_render.py) -----------------------------
     def tsdf_render_init(self, width: int, height: int, fx: float, fy: float, cx: float, cy: float,

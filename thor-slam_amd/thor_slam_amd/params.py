@@ -14,6 +14,7 @@ from .dense_align import DEFAULTS as ALIGN_DEFAULTS, check_align_params
 from .dense_dynamic import check_dynamic_params
 from .dense_freespace import check_freespace_params
 from .dense_follow import check_follow_params
+from .dense_store import check_store_params
 from .dense_loop import check_loop_params
 from .dense_rig import DenseCamerasError
 from .slam.interface import SlamConfig
@@ -155,6 +156,12 @@ class HipSlamConfig(SlamConfig):
     dense_follow_margin: int = 32
     dense_follow_step: int = 16
     dense_follow_anchor: tuple | None = None
+    # the brick store behind the window (thor_slam_amd/dense_store.py): what leaves the window is kept
+    # on the device in a pool of dense_store_bricks 8 x 8 x 8 bricks (14,336 B each with every layer
+    # on: 65,536 bricks are about 0.9 GB, about 0.27 GB for tsdf + weight) and comes back when the
+    # window returns; get_dense_store reads it.  Needs dense_follow and one device.
+    dense_store: bool = False
+    dense_store_bricks: int = 65536
     # dense-map outputs (get_mesh / get_esdf / get_esdf_slice; thor_slam_amd/dense.py): nvblox's
     # mesh / ESDF integrator parameters (its defaults: min weight 1e-4, ESDF max distance 2 m, site
     # distance 1 voxel) and the 2-D slice's height band (y down: metres in the tracking world)
@@ -342,6 +349,12 @@ class HipSlamConfig(SlamConfig):
                 # the camera-sharded RGB-D map lives on rank 0, behind the shard driver
                 raise ValueError("dense_follow does not run on a sharded rig (devices)")
             check_follow_params(self.dense_follow_margin, self.dense_follow_step, self.dense_follow_anchor)
+        if self.dense_store:
+            if not self.dense_follow:
+                raise ValueError("dense_store needs dense_follow=True (it keeps what leaves the rolling window)")
+            if self.devices:
+                raise ValueError("dense_store does not run on a sharded rig (devices)")
+            check_store_params(self.dense_store_bricks)
         if self.dense_align:
             if not self.dense_map:
                 raise ValueError("dense_align needs dense_map=True")

@@ -8,7 +8,8 @@ stereo matcher's (``thor_slam_amd/stereo_depth.py``) of every ``stereo_depth_int
 run (``tslam_tsdf_integrate_rig``) on the rig's body poses (``thor_slam_amd/dense_rig.py``).
 ``dense_follow`` lets the volume follow the camera in whole voxels, decided on the device once per
 integrated batch (``thor_slam_amd/dense_follow.py``); the readers then report the window's effective
-``origin`` and its ``window_shift``.  ``dense_align`` aligns a batch's depth to the map before it goes
+``origin`` and its ``window_shift``; with ``dense_store`` what leaves the window goes to a brick store
+on the device and comes back with the window (``thor_slam_amd/dense_store.py``).  ``dense_align`` aligns a batch's depth to the map before it goes
 in (``thor_slam_amd/dense_align.py``).  ``dense_loop`` keeps the map consistent with loop closure and
 relocalisation (``thor_slam_amd/dense_loop.py``): the map takes the pose-graph node frames, on the
 loop-corrected pose, keeps their depth in an archive on the device, and after the nodes' poses
@@ -27,6 +28,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from ..dense_freespace import split
+from ..dense_store import split_words
 from ..dense_render import check_render_params, scaled_intrinsics, view_in_volume
 from ..depth_register import DEFAULT_MAX_SPLAT, check_register_params, color_camera, compose_color_T_rect
 
@@ -106,6 +108,8 @@ class DenseMap:
             h.tsdf_dynamic_init(pair=0, rect=bool(cfg.stereo_depth), max_frames=cfg.batch_size, **cfg.dense_dynamic_params())
             if cfg.dense_dynamic_settle_frames:   # masked objects that come to rest are released (thor_slam_amd/dense_freespace.py)
                 h.tsdf_freespace_init(settle_frames=cfg.dense_dynamic_settle_frames, occupied_band_vox=cfg.dense_dynamic_band_vox)
+        if cfg.dense_store:   # what leaves the window is kept (thor_slam_amd/dense_store.py): after every layer exists
+            h.tsdf_store_init(cfg.dense_store_bricks)
         if cfg.stereo_depth:   # a stereo rig: the depth comes from the dense matcher (slots per camera)
             h.stereo_depth_init(max_frames=cfg.batch_size * max(1, len(self.dense)),
                                 uniqueness=cfg.stereo_depth_uniqueness, lr_tol=cfg.stereo_depth_lr_tol)
@@ -309,6 +313,17 @@ class DenseMap:
         run, settled = split(h.tsdf_freespace_read())
         shift, origin = h.tsdf_window()
         return {"run": run, "settled": settled, "origin": origin, "window_shift": shift, "world_T_volume": world_T_volume}
+
+    def store(self, world_T_volume: np.ndarray) -> dict:
+        cfg, h = self.cfg, self.h
+        freespace = bool(cfg.dense_dynamic and cfg.dense_dynamic_settle_frames)
+        bricks, words = h.tsdf_store_read()
+        out = split_words(words, self.color, freespace)
+        if freespace:
+            out["run"], out["settled"] = split(out.pop("freespace"))
+        return {**out, "bricks": bricks, "voxel_size": float(cfg.voxel_size),
+                "origin": np.array(cfg.tsdf_origin, dtype=np.float64), "world_T_volume": world_T_volume,
+                "stats": h.tsdf_store_stats()}
 
     def depth_image(self, pair: int) -> tuple | None:
         if pair not in self.sd_last:

@@ -507,6 +507,20 @@ class HipSlamEngine(SlamEngine):
         d = self._dense_reader(self._config.dense_dynamic and self._config.dense_dynamic_settle_frames > 0)
         return None if d is None else d.freespace(self._world_T_volume)
 
+    def get_dense_store(self) -> dict | None:
+        """What has left the rolling window (``dense_store``; the rule is thor_slam_amd/dense_store.py):
+        the store's n bricks of 8 x 8 x 8 voxels that hold a voxel, in ascending (bz, by, bx):
+        ``bricks`` i32 [n][3] (bx, by, bz), ``tsdf`` / ``weight`` f32 [n][8][8][8] (z, y, x), with the
+        colour layer ``color`` f32 [n][8][8][8][3] and ``color_weight``, with the free-space layer
+        ``run`` / ``settled`` as ``get_freespace`` splits them; ``voxel_size``, ``origin`` (the
+        configured ``tsdf_origin``: brick b's local voxel (i, j, k) is centred at
+        origin + voxel_size (8 b + (i, j, k) + 0.5)), ``world_T_volume`` and ``stats`` (capacity,
+        bricks allocated, bricks, voxels stored, voxels dropped, moves, words per voxel).
+        ``dense_store.assemble`` joins it with ``get_dense_map`` into the whole map.  None unless the
+        option is on.  Synchronises."""
+        d = self._dense_reader(self._config.dense_store)
+        return None if d is None else d.store(self._world_T_volume)
+
     def get_dense_map(self) -> dict | None:
         """The TSDF volume (nvblox-shaped): ``tsdf`` / ``weight`` f32 [nz][ny][nx] (metres of
         truncated signed distance; weight 0 = never observed), the voxel grid (``origin``,
