@@ -985,6 +985,35 @@ int tslam_tsdf_store_init(tslam_handle* h, int64_t capacity_bricks);
 int tslam_tsdf_store_stats(tslam_handle* h, int64_t* out8);
 int tslam_tsdf_store_read(tslam_handle* h, int64_t max_bricks, int32_t* brick_xyz, uint32_t* words, int64_t* n_bricks);
 
+/* The mesh of the whole dense map: marching cubes over the window and the brick store together
+ * (added within ABI 21: one new symbol; nothing else changes, and nothing new is launched or
+ * allocated unless it is called).  Spec: thor_slam_amd/dense_store.py, "The mesh of the whole map";
+ * tests/ref_tsdf_store_mesh.py restates it.
+ *
+ * The rules are tslam_mesh_extract's (the configuration byte, the triangle table, t = va / (va - ve)
+ * in f32, the colour of the nearer voxel), over the absolute voxel grid: absolute voxel a takes its
+ * value from the window when shift <= a < shift + dims on every axis, otherwise from its store brick
+ * floor(a / 8) when that is present, otherwise it is unobserved; the free-space words are ignored.
+ * A vertex on the edge from absolute voxel v along axis ax is (float)(o0 + s (v + 0.5)) per
+ * coordinate, f64, with o0 the configured (unshifted) origin, then p[ax] += t (float)s: it depends on
+ * absolute coordinates alone, never on where the window stands.  While the shift is zero it equals
+ * tslam_mesh_extract's vertex bit for bit; otherwise the two may differ in the last f32 bit, because
+ * the window's mesh adds s * shift to the origin first.  Triangles come brick by brick in ascending
+ * (bz, by, bx) of the brick floor(a / 8) of the cube's base corner a, within a brick in [k][j][i] of
+ * the base corner, within a cube in table order: for given map content the output is one fixed byte
+ * string.  The bricks visited are those the window's extent overlaps and every stored brick outside
+ * that range that holds a voxel (brick coordinates in [-2^20, 2^20), as the store's).
+ *
+ * tslam_mesh_extract_whole: extract into the handle's triangle (and, with the colour layer, colour)
+ *   buffer, which tslam_mesh_extract writes too: tslam_mesh_read / tslam_mesh_read_colors return
+ *   whichever mesh was extracted last.  Enqueued on `stream` (NULL: the handle's last stream) after
+ *   any move; it only reads the store.  *n_tris: the triangle count, *n_bricks: the bricks visited
+ *   (either may be NULL).  It waits for the brick list's length, the list itself (8 B per listed
+ *   brick to the host, sorted, and back) and the triangle count; no voxel and no table cell is
+ *   copied to the host.  TSLAM_ESTATE without a volume, without a store, or inside a batch;
+ *   TSLAM_EINVAL for min_weight negative or NaN. */
+int tslam_mesh_extract_whole(tslam_handle* h, double min_weight, int64_t* n_tris, int64_t* n_bricks, void* stream);
+
 /* The dense map seen from a pose: TSDF ray casting (added within ABI 21: four new symbols and a
  * struct; nothing else changes, and a handle that calls none of them behaves as before).  Spec:
  * thor_slam_amd/dense_render.py.  For every pixel of an undistorted pinhole camera at world_T_cam

@@ -306,6 +306,10 @@ void launch_mesh_count(const DenseArgs& a, uint8_t* cfg, uint32_t* block_sums, u
     hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(1024), 0, s, block_sums, (int)nb, block_off, total);
 }
 
+void launch_mesh_scan(const uint32_t* block_sums, int nb, uint64_t* block_off, uint64_t* total, hipStream_t s) {
+    hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(1024), 0, s, block_sums, nb, block_off, total);
+}
+
 void launch_mesh_emit(const DenseArgs& a, const uint8_t* cfg, const uint64_t* block_off, float* tris, float* cols,
                       int64_t cap, hipStream_t s) {
     hipLaunchKernelGGL(k_mesh_emit, dim3(blocks_for(a.n_cubes)), dim3(DENSE_THREADS), 0, s, a, cfg, block_off, tris, cols,

@@ -414,6 +414,24 @@ struct TsdfStore {
 void launch_tsdf_move(const TsdfLayers& l, const TsdfWindow* win, hipStream_t s, const TsdfStore* store = nullptr);
 void launch_tsdf_store_out(const TsdfLayers& l, const TsdfWindow* win, const TsdfStore& st, hipStream_t s);
 void launch_tsdf_store_in(const TsdfLayers& l, const TsdfWindow* win, const TsdfStore& st, hipStream_t s);
+// The mesh of the whole map (thor_slam_amd/dense_store.py; k_tsdf_store_mesh.hip): marching cubes over
+// the window and the store together, one block per listed store brick.  o is the configured,
+// unshifted origin; the kernels read the window's shift from the record.
+struct WmeshArgs {
+    const float* tsdf;         // the window's layers [nz][ny][nx]
+    const float* weight;
+    const float* color;        // [nz][ny][nx][3] or null (no vertex colours)
+    int nx, ny, nz;
+    double ox, oy, oz, s;
+    float sf, min_weight;
+    const TsdfWindow* win;
+    TsdfStore st;
+};
+// list: the keys of the bricks to visit, unsorted, *count of them (beyond `cap` nothing is written)
+void launch_wmesh_list(const WmeshArgs& a, int64_t cells, int64_t max_window, uint64_t* list, int64_t cap, uint32_t* count, hipStream_t s);
+void launch_wmesh_count(const WmeshArgs& a, const uint64_t* list, int64_t n_bricks, uint32_t* block_sums, hipStream_t s);
+void launch_wmesh_emit(const WmeshArgs& a, const uint64_t* list, int64_t n_bricks, const uint64_t* block_off, float* tris, float* cols,
+                       int64_t cap, hipStream_t s);
 // what a call's first chunk does between its poses and its integration when the window follows
 struct TsdfFollowCall {
     TsdfFollow f;
@@ -672,6 +690,8 @@ struct DenseArgs {
 };
 void launch_mesh_count(const DenseArgs& a, uint8_t* cfg, uint32_t* block_sums, uint64_t* block_off, uint64_t* total,
                        hipStream_t s);
+// k_mesh_scan alone: block_off[b] = sum of block_sums[0..b), *total = the sum of all
+void launch_mesh_scan(const uint32_t* block_sums, int nb, uint64_t* block_off, uint64_t* total, hipStream_t s);
 void launch_mesh_emit(const DenseArgs& a, const uint8_t* cfg, const uint64_t* block_off, float* tris, float* cols,
                       int64_t cap, hipStream_t s);
 void launch_esdf(const DenseArgs& a, int R, const float* tab, int32_t* g0, int32_t* g1, float* out, hipStream_t s);

@@ -267,6 +267,18 @@ struct tslam_handle {
     TsdfStore store{};
     int64_t store_cells = 0;
     size_t store_pool_bytes = 0;      // as allocated (for the layers tslam_tsdf_store_init found)
+    // ---- tslam_api_store_mesh.cpp ----
+    // the mesh of the whole map (tslam_mesh_extract_whole): the brick list, its pinned host copy for
+    // the sort, the per-brick triangle totals and first triangles; all sized on first use and grown
+    // on demand.  The triangles go to d_mesh_tris / d_mesh_cols, which the two extracts share.
+    uint64_t* d_wmesh_list = nullptr;   // [wmesh_list_cap] keys
+    int64_t wmesh_list_cap = 0;
+    uint32_t* d_wmesh_count = nullptr;  // the list's length
+    uint64_t* wmesh_host = nullptr;     // pinned
+    size_t wmesh_host_cap = 0;
+    uint32_t* d_wmesh_bsum = nullptr;   // [wmesh_bricks_cap]
+    uint64_t* d_wmesh_boff = nullptr;   // [wmesh_bricks_cap + 1]; the last one = the mesh's total
+    int64_t wmesh_bricks_cap = 0;
     // ---- tslam_api_render.cpp ----
     // the volume seen from a pose (tslam_tsdf_render_*): parameters, the camera's ray-length table,
     // the call's pose table and staged host poses, and the images [rnd_views][H][W] of every

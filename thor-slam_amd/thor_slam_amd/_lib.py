@@ -324,6 +324,8 @@ _SIGNATURES = {
     "tslam_mesh_read_colors": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
     "tslam_mesh_extract": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]),
     "tslam_mesh_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
+    "tslam_mesh_extract_whole": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.POINTER(ctypes.c_int64),
+                                                ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]),
     "tslam_esdf_compute": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
     "tslam_esdf_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "tslam_esdf_slice": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
@@ -1544,6 +1546,24 @@ class Handle:
         ``colors`` (colour layer) also the vertex colours [n][3][3] f32: (triangles, colours)."""
         n = ctypes.c_int64()
         _check(self.lib.tslam_mesh_extract(self.h, float(min_weight), ctypes.byref(n), ctypes.c_void_p(stream)))
+        out = np.zeros((n.value, 3, 3), dtype=np.float32)
+        _check(self.lib.tslam_mesh_read(self.h, out.ctypes.data, int(n.value)))
+        if not colors:
+            return out
+        col = np.zeros((n.value, 3, 3), dtype=np.float32)
+        if n.value:
+            _check(self.lib.tslam_mesh_read_colors(self.h, col.ctypes.data, int(n.value)))
+        return out, col
+
+    def mesh_whole(self, min_weight: float = 1e-4, stream: int = 0, colors: bool = False):
+        """The mesh of the whole map, window and brick store together (thor_slam_amd/dense_store.py):
+        what ``mesh`` returns, brick by brick in ascending (bz, by, bx), vertices from absolute voxel
+        coordinates and the configured origin.  ``mesh_whole_bricks`` is the number of bricks visited.
+        The two extracts share the handle's buffer (synchronises)."""
+        n, nb = ctypes.c_int64(), ctypes.c_int64()
+        _check(self.lib.tslam_mesh_extract_whole(self.h, float(min_weight), ctypes.byref(n), ctypes.byref(nb),
+                                                 ctypes.c_void_p(stream)))
+        self.mesh_whole_bricks = int(nb.value)
         out = np.zeros((n.value, 3, 3), dtype=np.float32)
         _check(self.lib.tslam_mesh_read(self.h, out.ctypes.data, int(n.value)))
         if not colors:

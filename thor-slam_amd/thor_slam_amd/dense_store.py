@@ -37,12 +37,42 @@ device and comes back when the window returns.  This file is the spec, with a sm
   ``tslam_tsdf_color`` and ``tslam_tsdf_freespace_init``, and while the store is on the free-space
   layer can be neither added nor freed (``TSLAM_ESTATE``).  The depth archive and the store refuse
   each other, as the archive and following do.
+
+**The mesh of the whole map** (``tslam_mesh_extract_whole``; ``Handle.mesh_whole``;
+``HipSlamEngine.get_mesh(whole=True)``; ``k_wmesh_list`` / ``k_wmesh_count`` / ``k_wmesh_emit`` in
+``k_tsdf_store_mesh.hip``; the model is ``whole_mesh`` below, ``tests/ref_tsdf_store_mesh.py`` restates
+it).  Marching cubes by the rules of ``thor_slam_amd/dense.py``, unchanged — the configuration byte,
+``tslam_mc_table.h``, ``t = va / (va - ve)`` in f32, the colour of the nearer voxel — over the
+absolute voxel grid above, window and store together, with no seam.
+
+* **A voxel's value.**  Absolute voxel ``a`` takes its (tsdf, weight, colour) from the window when
+  ``shift <= a < shift + dims`` on every axis; otherwise from its store brick ``floor(a / 8)`` when
+  that brick is present; otherwise it is zero, and so unobserved.  The window and the store never
+  hold the same voxel, so there is no precedence to decide.  The free-space word is ignored.
+* **A cube** with base corner ``a`` has corners ``a + (n & 1, n >> 1 & 1, n >> 2 & 1)`` and is meshed
+  when all 8 have weight >= ``min_weight``.  It belongs to brick ``floor(a / 8)``.
+* **A vertex** on the edge from base voxel ``v`` along axis ``ax``: coordinate c is
+  ``(float)(o0[c] + s * (v[c] + 0.5))`` in f64, with ``o0`` the configured, unshifted origin and ``v``
+  absolute; then ``p[ax] += t * (float)s``.  The position depends on absolute coordinates alone,
+  never on where the window stands.  While the shift is zero it equals ``tslam_mesh_extract``'s
+  vertex bit for bit; otherwise the two may differ in the last f32 bit, because the window's mesh
+  adds ``s * shift`` to the origin first.
+* **Order.**  Bricks in ascending (bz, by, bx), the numeric order of ``store_key``; within a brick
+  [k][j][i] of the cube's base corner; within a cube table order.  For given map content the output
+  is one fixed byte string, wherever the window is.
+* **Bricks visited:** every brick the window's extent overlaps, and every stored brick outside that
+  range that holds a voxel.  A cube whose base brick is in neither set has an unobserved base corner,
+  so these are all that need visiting.  As in the store, a brick whose coordinate lies outside
+  ``[-2^20, 2^20)`` on an axis has no key: it is not visited, and not looked up as a source.
+* The mesh only reads the store and shares the handle's triangle buffer with ``tslam_mesh_extract``:
+  the readers return whichever was extracted last.
 """
 
 from __future__ import annotations
 
 import numpy as np
 
+from .dense import mc_triangle_table
 from .dense_follow import LIMIT, move_layer
 
 B = 8                      # TSDF_STORE_B
@@ -189,3 +219,79 @@ def assemble(window: dict, store: dict, lo, hi) -> dict:
         paste(win, np.asarray(window["window_shift"], dtype=np.int64))
         out[key] = dst
     return out
+
+
+def _coord_ok(b) -> bool:
+    return all(-COORD_LIMIT <= int(v) < COORD_LIMIT for v in b)
+
+
+def whole_mesh(window: dict, store: dict, origin, voxel_size: float, min_weight: float, colors: bool = False):
+    """The model of ``tslam_mesh_extract_whole``: ``window`` holds ``tsdf`` / ``weight`` f32
+    [nz][ny][nx], ``window_shift`` and, for ``colors``, ``color`` [nz][ny][nx][3]; ``store`` holds
+    ``bricks`` i32 [n][3] and ``tsdf`` / ``weight`` [n][8][8][8] (and ``color`` [n][8][8][8][3]), as
+    ``get_dense_map()`` and ``get_dense_store()`` give them; ``origin`` is the configured one.
+    -> (triangles f32 [m][3][3], colours f32 [m][3][3] or None, bricks visited)."""
+    count, table = mc_triangle_table()
+    lo = np.array(window["window_shift"], dtype=np.int64)
+    names = ("tsdf", "weight") + (("color",) if colors else ())
+    win = {k: np.asarray(window[k], np.float32) for k in names}
+    dims = np.array(win["tsdf"].shape[::-1], dtype=np.int64)
+    stored = {}
+    for r, b in enumerate(np.asarray(store["bricks"], dtype=np.int64).reshape(-1, 3)):
+        stored[tuple(int(v) for v in b)] = {k: np.asarray(store[k][r], np.float32) for k in names}
+    b0, b1 = brick_of(lo)[0], brick_of(lo + dims - 1)[0]
+    visit = {(x, y, z) for z in range(int(b0[2]), int(b1[2]) + 1) for y in range(int(b0[1]), int(b1[1]) + 1)
+             for x in range(int(b0[0]), int(b1[0]) + 1)}
+    visit |= set(stored)                              # the store's content: every brick there holds a voxel
+    visit = sorted((b for b in visit if _coord_ok(b)), key=lambda b: (b[2], b[1], b[0]))
+    o0, s, sf = [float(v) for v in origin], float(voxel_size), np.float32(voxel_size)
+    tz, ty, tx = np.meshgrid(np.arange(9), np.arange(9), np.arange(9), indexing="ij")
+    corner = [tuple(slice(d, B + d) for d in (n >> 2 & 1, n >> 1 & 1, n & 1)) for n in range(8)]
+    tris, cols = [], []
+    for b in visit:
+        # the 9 x 9 x 9 corner tile: first the 8 source bricks b + {0, 1}^3 that are present, then,
+        # voxel by voxel (a window edge can cut a brick), the window's value wherever the window is
+        tile = {k: np.zeros((9, 9, 9) + win[k].shape[3:], np.float32) for k in names}
+        for n in range(8):
+            bits = (n >> 2 & 1, n >> 1 & 1, n & 1)   # z, y, x
+            sb = (b[0] + bits[2], b[1] + bits[1], b[2] + bits[0])
+            src = stored.get(sb) if _coord_ok(sb) else None
+            if src is not None:
+                at = tuple(slice(8, 9) if d else slice(0, 8) for d in bits)
+                part = tuple(slice(0, 1) if d else slice(0, 8) for d in bits)
+                for k in names:
+                    tile[k][at] = src[k][part]
+        w = [B * b[0] + tx - lo[0], B * b[1] + ty - lo[1], B * b[2] + tz - lo[2]]
+        inwin = np.ones((9, 9, 9), bool)
+        for c in range(3):
+            inwin &= (w[c] >= 0) & (w[c] < dims[c])
+        for k in names:
+            tile[k][inwin] = win[k][w[2][inwin], w[1][inwin], w[0][inwin]]
+        obs = np.ones((B, B, B), bool)
+        cfgs = np.zeros((B, B, B), np.int64)
+        for n in range(8):
+            obs &= tile["weight"][corner[n]] >= np.float32(min_weight)
+            cfgs |= (tile["tsdf"][corner[n]] < 0).astype(np.int64) << n
+        cfgs[~obs] = 0
+        for k, j, i in zip(*(x.tolist() for x in np.nonzero(count[cfgs]))):   # row-major: [k][j][i]
+            cfg = int(cfgs[k, j, i])
+            for t in range(int(count[cfg])):
+                v, vc = [], []
+                for e in table[cfg, t]:
+                    ax, m = divmod(int(e), 4)
+                    o = [c for c in range(3) if c != ax]
+                    off = [0, 0, 0]
+                    off[o[0]], off[o[1]] = m & 1, m >> 1
+                    base = (i + off[0], j + off[1], k + off[2])
+                    end = tuple(base[c] + (c == ax) for c in range(3))
+                    va, ve = tile["tsdf"][base[::-1]], tile["tsdf"][end[::-1]]
+                    tt = va / (va - ve)                                           # f32
+                    p = [np.float32(o0[c] + s * ((B * b[c] + base[c]) + 0.5)) for c in range(3)]
+                    p[ax] = p[ax] + tt * sf
+                    v.append(p)
+                    if colors:
+                        vc.append(tile["color"][base[::-1]] if tt < np.float32(0.5) else tile["color"][end[::-1]])
+                tris.append(v)
+                cols.append(vc)
+    out = np.array(tris, dtype=np.float32).reshape(-1, 3, 3)
+    return out, (np.array(cols, dtype=np.float32).reshape(-1, 3, 3) if colors else None), len(visit)

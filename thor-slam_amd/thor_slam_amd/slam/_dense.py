@@ -390,6 +390,17 @@ class DenseMap:
             return {"triangles": tris, "colors": cols, "world_T_volume": world_T_volume}
         return {"triangles": self.h.mesh(cfg.mesh_integrator_min_weight), "world_T_volume": world_T_volume}
 
+    def mesh_whole(self, world_T_volume: np.ndarray) -> dict:
+        """The window and the brick store in one mesh (thor_slam_amd/dense_store.py)."""
+        cfg, h = self.cfg, self.h
+        out = {}
+        if self.color:
+            out["triangles"], out["colors"] = h.mesh_whole(cfg.mesh_integrator_min_weight, colors=True)
+        else:
+            out["triangles"] = h.mesh_whole(cfg.mesh_integrator_min_weight)
+        return {**out, "world_T_volume": world_T_volume, "origin": np.array(cfg.tsdf_origin, dtype=np.float64),
+                "bricks": h.mesh_whole_bricks}
+
     def esdf(self, world_T_volume: np.ndarray) -> dict:
         cfg = self.cfg
         esdf = self.h.esdf(cfg.esdf_integrator_max_distance_m, cfg.esdf_integrator_max_site_distance_vox,

@@ -562,10 +562,20 @@ class HipSlamEngine(SlamEngine):
         body[:3, 3] = pose.position
         return body @ self._base_T_rect
 
-    def get_mesh(self) -> dict | None:
+    def get_mesh(self, whole: bool = False) -> dict | None:
         """The surface mesh of the TSDF volume (marching cubes on the device, k_dense.hip):
         ``triangles`` f32 [n][3][3] (metres in the tracking world, facing free space), with the
-        colour layer ``colors`` f32 [n][3][3] (R, G, B per vertex), and ``world_T_volume``.  None unless ``dense_map`` is on.  Synchronises."""
+        colour layer ``colors`` f32 [n][3][3] (R, G, B per vertex), and ``world_T_volume``.  None unless ``dense_map`` is on.  Synchronises.
+
+        ``whole=True`` (``dense_store``; k_tsdf_store_mesh.hip, the rule is thor_slam_amd/dense_store.py):
+        one mesh of everything the map holds, the rolling window and the brick store together, with
+        no seam between them: the same keys, with ``origin`` (the configured ``tsdf_origin``, which
+        the vertices are computed from: they do not depend on where the window stands) and
+        ``bricks`` (the 8 x 8 x 8 store bricks visited).  Triangles come brick by brick in ascending
+        (bz, by, bx).  None unless ``dense_store`` is on."""
+        if whole:
+            d = self._dense_reader(self._config.dense_store)
+            return None if d is None else d.mesh_whole(self._world_T_volume)
         d = self._dense_reader()
         return None if d is None else d.mesh(self._world_T_volume)
 
